@@ -17,6 +17,13 @@ reported, with the residual start skew (``start_skew_us``).  Metric = global cel
 child process and relays its output (it never measures one GPU in place of N).  A progress watchdog
 (``--watchdog`` seconds) makes every rank exit non-zero if a peer hangs or RCCL fails.  Without a
 GPU it falls back to the CPU backend on BASELINE config 1 (256^2).
+
+A run without further options does only what the headline figure needs: set up, warm up, time the K
+generations, print the record.  ``--full`` adds the measurements that take runs of their own after the
+timed one (the per-phase probe, ``phases`` in the record).  ``--dump-outputs DIR`` writes the board the
+timed run computed (a fixed sample of its cells and its row / column populations) as ``.npy`` arrays;
+the board is seeded (``--seed``), so two builds run with the same arguments can be compared array for
+array.
 """
 from __future__ import annotations
 
@@ -61,9 +68,60 @@ def parse_args(argv=None):
                          "through host memory instead of failing")
     ap.add_argument("--watchdog", type=float, default=float(os.environ.get("GOL_WATCHDOG", "120")),
                     help="seconds without progress (or an RCCL error) before every rank aborts non-zero (0 = off)")
-    ap.add_argument("--no-phases", action="store_true", help="skip the untimed per-phase probe after the run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed run, also take the measurements that need runs of their own (the "
+                         "untimed per-phase probe: `phases`); a run without it only sets up, warms up and times")
+    ap.add_argument("--no-phases", action="store_true", help="with --full: skip the per-phase probe after the run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed run, write what it computed (the board after warmup + steps "
+                         "generations) to DIR as .npy arrays: see dump_outputs()")
     ap.add_argument("--seed", type=int, default=0x5EED)
     return ap.parse_args(argv)
+
+
+DUMP_SAMPLE = (2048, 4096)  # rows x columns of the dumped board sample (float32: 32 MiB over all ranks)
+DUMP_SAMPLE_SEED = 0xD0A7
+DUMP_POPULATION_CELLS = 1 << 32  # 65536^2
+
+
+def dump_outputs(dirname, sim, rank, P, population):
+    """``--dump-outputs DIR``: the board the timed run left behind, as float arrays two builds can be
+    compared by.  Every rank writes its own tile's arrays (``<name>.npy``, or ``<name>_rank<r>.npy`` when
+    there are several ranks):
+
+      board_sample    float32 (rows, cols): the tile's cells (0/1) at a fixed sample of its rows and
+                      columns (sorted, drawn without replacement by numpy's default_rng(DUMP_SAMPLE_SEED):
+                      the same cells for the same tile shape), DUMP_SAMPLE cells over all ranks at most
+      row_population  float64 (h,): live cells of every row of the tile (the whole tile, not the sample)
+      col_population  float64 (w,): live cells of every column of the tile (both only for tiles of at
+                      most DUMP_POPULATION_CELLS cells: they are counted on the host)
+      population      float64 (1,): live cells of the global board (rank 0 only)
+    """
+    import numpy as np
+
+    from gol_amd.ops.bitpack import unpack_words
+
+    os.makedirs(dirname, exist_ok=True)
+    suffix = "" if P == 1 else f"_rank{rank}"
+    h, w = sim.geometry.h, sim.geometry.w
+    words = sim.words()  # (h, ceil(w/64)) uint64
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    rows = np.sort(rng.choice(h, size=min(h, max(1, DUMP_SAMPLE[0] // P)), replace=False))
+    cols = np.sort(rng.choice(w, size=min(w, DUMP_SAMPLE[1]), replace=False))
+    sample = unpack_words(words[rows], w)[:, cols].astype(np.float32)
+    np.save(os.path.join(dirname, f"board_sample{suffix}.npy"), sample)
+    if h * w <= DUMP_POPULATION_CELLS:
+        row_pop = np.empty(h, dtype=np.float64)
+        col_pop = np.zeros(w, dtype=np.float64)
+        slab_rows = max(1, (1 << 25) // w)  # unpacked in slabs of 32 MiB: a 32768^2 tile is 1 GiB as bytes
+        for r0 in range(0, h, slab_rows):
+            slab = unpack_words(words[r0:r0 + slab_rows], w)
+            row_pop[r0:r0 + slab.shape[0]] = slab.sum(axis=1, dtype=np.int64)
+            col_pop += slab.sum(axis=0, dtype=np.int64)
+        np.save(os.path.join(dirname, f"row_population{suffix}.npy"), row_pop)
+        np.save(os.path.join(dirname, f"col_population{suffix}.npy"), col_pop)
+    if rank == 0:
+        np.save(os.path.join(dirname, "population.npy"), np.array([population], dtype=np.float64))
 
 
 def rank_problems(ranks, P, rccl_ranks):
@@ -272,9 +330,11 @@ def main() -> int:
     pop = sim.population()
     st = sim.stats()
     halo_bytes = transport.allreduce_sum(int(st["halo_bytes"]))  # all ranks, init + warmup + timed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, sim, rank, P, pop)  # before the probe below runs anything more
     k_timed = st["depth"] if steps >= st["depth"] else steps
     phases = None
-    if backend == "hip" and not args.no_phases:
+    if backend == "hip" and args.full and not args.no_phases:
         ph = sim.engine.phase_probe(min(steps, st["depth"]))
         phases = {"superstep_gens": int(ph.get("superstep_gens", k_timed)),
                   "timed_supersteps": -(-steps // max(1, int(ph.get("superstep_gens", k_timed))))}

@@ -20,6 +20,16 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _ranks_env(ranks):
+    """Environment for a ``ranks``-process launch.  This file checks the driver contract, not the GPU data
+    plane (tests/test_gpu_rccl.py does): on a machine with GPUs but fewer than one per rank, where RCCL
+    refuses ranks that share a device, the ranks run the CPU backend, as on a machine without a GPU."""
+    import gol_amd
+
+    n = gol_amd.native.hip_device_count()
+    return {"HIP_VISIBLE_DEVICES": "-1"} if 0 < n < ranks else {}
+
+
 def _run(cmd, env_extra=None):
     env = dict(os.environ, OMP_NUM_THREADS="1")
     env.pop("WORLD_SIZE", None)
@@ -48,6 +58,49 @@ def test_bench_single_process():
         assert out["sched_predicted_us_per_gen"] is None and out["predicted_over_measured"] is None
 
 
+def test_bench_plain_run_takes_no_phase_probe():
+    """A run without --full measures its headline figure only; --full adds `phases` (HIP engines)."""
+    cmd = [sys.executable, "bench.py", "--size", "256", "--steps", "20", "--warmup", "2"]
+    plain = _run(cmd)
+    assert plain["phases"] is None and plain["ms_per_step"] > 0
+    full = _run(cmd + ["--full"])
+    assert "phases" in full
+    if full["config"]["backend"] == "hip":
+        assert full["phases"]["superstep_us_max"] > 0, full["phases"]
+    assert _run(cmd + ["--full", "--no-phases"])["phases"] is None
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the board after warmup + steps generations: float arrays within 64 MB, the
+    same from run to run, and equal to the numpy oracle's board at the sampled cells."""
+    import numpy as np
+
+    sys.path.insert(0, REPO)
+    import bench
+    from gol_amd.ops import initial_board, numpy_step
+
+    outs = []
+    for d in ("a", "b"):
+        outs.append(_run([sys.executable, "bench.py", "--size", "256", "--steps", "20", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path / d)]))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["board_sample.npy", "col_population.npy", "population.npy", "row_population.npy"]
+    assert sorted(os.listdir(tmp_path / "b")) == names
+    a = {n: np.load(tmp_path / "a" / n) for n in names}
+    assert sum(v.nbytes for v in a.values()) <= 64e6
+    for n in names:
+        assert a[n].dtype in (np.float32, np.float64), (n, a[n].dtype)
+        assert np.array_equal(a[n], np.load(tmp_path / "b" / n)), n
+    ref = numpy_step(initial_board(5, 256, 1, True, 0x5EED), 22)
+    rng = np.random.default_rng(bench.DUMP_SAMPLE_SEED)
+    rows = np.sort(rng.choice(256, size=256, replace=False))
+    cols = np.sort(rng.choice(256, size=256, replace=False))
+    assert np.array_equal(a["board_sample.npy"], ref[np.ix_(rows, cols)].astype(np.float32))
+    assert np.array_equal(a["row_population.npy"], ref.sum(axis=1))
+    assert np.array_equal(a["col_population.npy"], ref.sum(axis=0))
+    assert a["population.npy"][0] == ref.sum() == outs[0]["config"]["population"]
+
+
 def test_bench_prediction_fields():
     sys.path.insert(0, REPO)
     import bench
@@ -61,7 +114,7 @@ def test_bench_prediction_fields():
 def test_bench_torchrun_two_ranks():
     out = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
-                "--steps", "20", "--warmup", "2"])
+                "--steps", "20", "--warmup", "2"], _ranks_env(2))
     cfg = out["config"]
     assert cfg["parallelism"].endswith("p2 (1x2)")
     # per-rank diagnosis arrays, one entry per rank, consistent with the aggregates
@@ -83,7 +136,7 @@ def test_bench_reports_start_skew():
 
 def test_bench_without_launcher_starts_the_ranks():
     """The driver's --gpus N run, mis-launched as a plain process, still measures N ranks."""
-    out = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "2"])
+    out = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "2"], _ranks_env(2))
     assert out["config"]["parallelism"].endswith("p2 (1x2)")
     assert out["config"]["board"][0] == 2 * out["config"]["tile_per_rank"][0]
 
@@ -102,7 +155,7 @@ def test_bench_rank_count_mismatch_fails():
 def test_bench_hung_rank_ends_the_job():
     """GOL_FAULT hangs rank 1 inside its run: its watchdog aborts it (exit 4) and the launcher ends the
     job non-zero within a bounded time, instead of the job hanging until the driver's timeout."""
-    env = dict(os.environ, OMP_NUM_THREADS="1", GOL_FAULT="1:10:hang")
+    env = dict(os.environ, OMP_NUM_THREADS="1", GOL_FAULT="1:10:hang", **_ranks_env(2))
     env.pop("WORLD_SIZE", None)
     t0 = time.monotonic()
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",

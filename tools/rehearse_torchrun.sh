@@ -18,10 +18,10 @@ PY
 run8() {
   tag=$1; shift
   start=$(date +%s.%N)
-  timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 1000)) bench.py --gpus 8 --steps 20 --warmup 5 --allow-host-staging "$@" > $O/$tag.json 2> $O/$tag.err
+  timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port $((29500 + RANDOM % 1000)) bench.py --gpus 8 --steps 20 --warmup 5 --full --allow-host-staging "$@" > $O/$tag.json 2> $O/$tag.err
   rc=$?
   end=$(date +%s.%N)
-  echo "== $tag: torch.distributed.run --nproc-per-node 8 bench.py --gpus 8 --steps 20 --warmup 5 --allow-host-staging $*" >> $O/summary.txt
+  echo "== $tag: torch.distributed.run --nproc-per-node 8 bench.py --gpus 8 --steps 20 --warmup 5 --full --allow-host-staging $*" >> $O/summary.txt
   echo "   rc=$rc wall=$(python -c "print(round($end-$start,1))")s" >> $O/summary.txt
   [ $rc -eq 0 ] && summ $O/$tag.json "  " >> $O/summary.txt
   return $rc
