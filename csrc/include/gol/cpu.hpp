@@ -9,15 +9,18 @@
 
 #include "gol/geometry.hpp"
 #include "gol/pattern.hpp"
+#include "gol/rule.hpp"
 
 namespace gol {
 namespace cpu {
 
-// One generation for rows [r_lo, r_hi) (all words -1 .. nw) of `dst` from `src`.
-void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi);
+// One generation for rows [r_lo, r_hi) (all words -1 .. nw) of `dst` from `src`.  B3/S23 runs the
+// specialised gates (bits.hpp rule64); any other rule a generic bit-sliced path (4-plane count, then
+// next = x ? S[count] : B[count] from the rule's masks), chosen once per call.
+void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, const Rule& rule = Rule());
 
 // k generations (k <= L.R).  Ping-pongs between a and b; returns the buffer with the result.
-u64* superstep(u64* a, u64* b, const Layout& L, int k);
+u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule = Rule());
 
 // x-periodic ghost words (and tail ghost bits) for rows [r_lo, r_hi).
 void fill_ghost_cols_wrap(u64* buf, const Layout& L, i64 r_lo, i64 r_hi);

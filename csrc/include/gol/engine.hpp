@@ -26,6 +26,7 @@
 #include "gol/geometry.hpp"
 #include "gol/pattern.hpp"
 #include "gol/plan.hpp"
+#include "gol/rule.hpp"
 #include "gol/transport.hpp"
 #include "gol/watchdog.hpp"
 
@@ -48,7 +49,10 @@ struct EngineConfig {
     int waves_target = 0;             // plan wave-count target (0 = auto)
     int plan_xcds = 8;                // XCD-aware plan order (workgroup b runs on XCD b % n; 1 = off)
     std::string kernel = "auto";      // auto (timed at init) | temporal (register pipeline) |
-                                      // tile (LDS-resident) | lds (1 gen, reference-class LDS tile)
+                                      // tile (LDS-resident) | lds (1 gen, reference-class LDS tile) |
+                                      // rule (the generic life-like-rule kernel, also for B3/S23)
+    Rule rule;                        // the life-like rule (default B3/S23; GOL_RULE).  Any other rule runs
+                                      // the generic paths: cpu::step_rows' bit-sliced count, step_rule on HIP
     int tile_waves = 8;               // tile kernel: waves per workgroup (4, 8, 16)
     bool tune_tile_waves = true;      // GOL_KERNEL=auto may also try 8 waves (false: GOL_TILE_WAVES set)
     std::string transport = "auto";   // auto | device | host  (host = stage halos through host memory)
@@ -94,7 +98,8 @@ struct EngineStats {
     int predicted_gens = 0;     // generations of the timed supersteps behind it
     double t_exchange_ms = 0;  // profile only
     double t_compute_ms = 0;   // profile only
-    std::string kernel;        // stencil kernel in use (HIP: temporal | tile | lds; CPU: cpu)
+    std::string kernel;        // stencil kernel in use (HIP: temporal | tile | lds | rule@K; CPU: cpu)
+    std::string rule;          // the rule, canonical (B3/S23)
     std::string schedule;      // superstep schedule: local (no neighbours) | split | full
     std::string tuning;        // init-time measurements behind the auto choices (HIP)
     bool registered = false;   // HIP + RCCL: the boards are registered with the communicator (zero-copy halos)

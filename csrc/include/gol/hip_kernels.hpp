@@ -5,6 +5,8 @@
 //                       streaming, bit-sliced v_bitop3/v_alignbit adders, DPP wave_shr/shl lane
 //                       exchange, K-deep register pipeline (temporal blocking), periodic wrap by
 //                       load addressing.  Replaces gol_kernel + the per-generation sync/swap.
+//   step_rule<K>      — step_temporal's streaming wave with a generic finish: any B0-free life-like rule
+//                       B.../S... from two run-time masks (rule_kernel.hip; K = 1..8).
 //   step_lds          — single-generation LDS-tiled variant (tile + ghost words staged in LDS);
 //                       kept as a measured alternative (GOL_KERNEL=lds).
 //   fill_ghost_cols   — x-periodic ghost words for widths that are not a multiple of 64.
@@ -22,6 +24,7 @@
 
 #include "gol/geometry.hpp"
 #include "gol/plan.hpp"
+#include "gol/rule.hpp"
 
 namespace gol {
 namespace hipk {
@@ -70,6 +73,14 @@ int max_step_depth();
 // Launch K generations: src -> dst over the waves of `plan` (n_waves * 64 LaneDescs in device memory).
 void launch_step(int k, const u64* src, u64* dst, const LaneDesc* plan, i64 n_waves, const StepParams& p,
                  hipStream_t s);
+// step_rule<K> (rule_kernel.hip): K generations of `rule` over the waves of `plan`, the same plans and
+// StepParams as launch_step (STEP_SEAM excepted: it has no seam-reading variant).  It reads and writes
+// exactly the rows and words step_temporal<K> does for the same plan.  Depths 1 .. max_rule_depth().
+bool rule_depth_supported(int k);
+int max_rule_depth();
+int rule_blocks_per_cu(int k, u32 flags);
+void launch_step_rule(int k, const Rule& rule, const u64* src, u64* dst, const LaneDesc* plan, i64 n_waves,
+                      const StepParams& p, hipStream_t s);
 // LDS-resident temporal kernel (step_tile): one workgroup of `nw_per_wg` (4, 8, 16) waves per plan
 // wave; `rows` = the plan's rows per chunk (<= tile_max_rows(k), the 160 KiB LDS limit).
 constexpr size_t kMaxLdsBytes = 160 * 1024;

@@ -105,6 +105,7 @@ py::dict stats_dict(const EngineStats& s) {
     d["t_exchange_ms"] = s.t_exchange_ms;
     d["t_compute_ms"] = s.t_compute_ms;
     d["kernel"] = s.kernel;
+    d["rule"] = s.rule;
     d["schedule"] = s.schedule;
     d["kernel_depth"] = s.kernel_depth;
     d["tile_waves"] = s.tile_waves;
@@ -266,7 +267,26 @@ PYBIND11_MODULE(_gol, m) {
         .def_readwrite("sched", &EngineConfig::sched)
         .def_readwrite("kernel_depth", &EngineConfig::kernel_depth)
         .def_readwrite("graph_rccl", &EngineConfig::graph_rccl)
-        .def_readwrite("plan_xcds", &EngineConfig::plan_xcds);
+        .def_readwrite("plan_xcds", &EngineConfig::plan_xcds)
+        // the life-like rule as a string (any form Rule::parse takes; reads back canonical, B3/S23)
+        .def_property(
+            "rule", [](const EngineConfig& c) { return c.rule.str(); },
+            [](EngineConfig& c, const std::string& s) {
+                try {
+                    c.rule = Rule::parse(s);
+                } catch (const Error& e) {
+                    throw py::value_error(e.what());
+                }
+            });
+    // rule string -> (birth, survive): bit c of birth / survive = a dead / live cell with c live neighbours lives
+    m.def("parse_rule", [](const std::string& s) {
+        try {
+            const Rule r = Rule::parse(s);
+            return py::make_tuple((unsigned)r.birth, (unsigned)r.survive);
+        } catch (const Error& e) {
+            throw py::value_error(e.what());
+        }
+    });
 
     py::class_<Engine>(m, "Engine")
         .def_static(

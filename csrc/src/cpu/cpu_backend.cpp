@@ -8,7 +8,66 @@
 namespace gol {
 namespace cpu {
 
-void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi) {
+namespace {
+
+// Generic life-like rule, still bit-packed: the four planes of T (the 3x3 sum including the centre, 0..9)
+// from the three rows' horizontal sums, then next = x ? S[T - 1] : B[T] as two mux trees over T whose
+// leaves are all-ones / all-zeros words built once per call from the rule's masks.
+struct RuleLeaves {
+    u64 b[10], s[10];  // by T: dead-centre and live-centre outcome
+    explicit RuleLeaves(const Rule& r) {
+        for (int t = 0; t < 10; ++t) {
+            b[t] = (t <= 8 && ((r.birth >> t) & 1u)) ? ~0ull : 0ull;        // (T = 9 has a live centre)
+            s[t] = (t >= 1 && ((r.survive >> (t - 1)) & 1u)) ? ~0ull : 0ull;  // (T = 0 has a dead centre)
+        }
+    }
+};
+
+inline u64 mux64(u64 sel, u64 one, u64 zero) { return (sel & one) | (~sel & zero); }
+
+inline u64 tree64(const u64* f, u64 t0, u64 t1, u64 t2, u64 t3) {
+    const u64 m01 = mux64(t0, f[1], f[0]), m23 = mux64(t0, f[3], f[2]);
+    const u64 m45 = mux64(t0, f[5], f[4]), m67 = mux64(t0, f[7], f[6]);
+    const u64 lo = mux64(t2, mux64(t1, m67, m45), mux64(t1, m23, m01));
+    return mux64(t3, mux64(t0, f[9], f[8]), lo);  // T >= 8: t2 = t1 = 0
+}
+
+inline u64 rule64_generic(u64 a0, u64 a1, u64 b0, u64 b1, u64 c0, u64 c1, u64 x, const RuleLeaves& f) {
+    const u64 x0 = a0 ^ b0 ^ c0;
+    const u64 cy = (a0 & b0) | (a0 & c0) | (b0 & c0);
+    const u64 u0 = a1 ^ b1 ^ c1;
+    const u64 u1 = (a1 & b1) | (a1 & c1) | (b1 & c1);
+    // T = x0 + 2 (cy + u0 + 2 u1)
+    const u64 t1 = cy ^ u0, k = cy & u0, t2 = u1 ^ k, t3 = u1 & k;
+    return mux64(x, tree64(f.s, x0, t1, t2, t3), tree64(f.b, x0, t1, t2, t3));
+}
+
+void step_rows_generic(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, const Rule& rule) {
+    const RuleLeaves f(rule);
+    const i64 n = L.nw + 2;  // words -1 .. nw
+#pragma omp parallel for schedule(static) if ((r_hi - r_lo) * n > 16384)
+    for (i64 r = r_lo; r < r_hi; ++r) {
+        const u64* up = src + L.index(r - 1, -1);
+        const u64* mid = src + L.index(r, -1);
+        const u64* dn = src + L.index(r + 1, -1);
+        u64* out = dst + L.index(r, -1);
+        for (i64 j = 0; j < n; ++j) {
+            u64 pu = j ? up[j - 1] : 0, nu = j + 1 < n ? up[j + 1] : 0;
+            u64 pm = j ? mid[j - 1] : 0, nm = j + 1 < n ? mid[j + 1] : 0;
+            u64 pd = j ? dn[j - 1] : 0, nd = j + 1 < n ? dn[j + 1] : 0;
+            u64 a0, a1, b0, b1, c0, c1;
+            hsum64(pu, up[j], nu, a0, a1);
+            hsum64(pm, mid[j], nm, b0, b1);
+            hsum64(pd, dn[j], nd, c0, c1);
+            out[j] = rule64_generic(a0, a1, b0, b1, c0, c1, mid[j], f);
+        }
+    }
+}
+
+}  // namespace
+
+void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, const Rule& rule) {
+    if (!rule.is_conway()) return step_rows_generic(src, dst, L, r_lo, r_hi, rule);  // (one branch per call)
     const i64 n = L.nw + 2;  // words -1 .. nw
 #pragma omp parallel for schedule(static) if ((r_hi - r_lo) * n > 16384)
     for (i64 r = r_lo; r < r_hi; ++r) {
@@ -29,13 +88,13 @@ void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi) {
     }
 }
 
-u64* superstep(u64* a, u64* b, const Layout& L, int k) {
+u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule) {
     if (k < 1 || k > L.R) throw Error(strprintf("superstep depth %d outside 1..%d", k, L.R));
     u64* src = a;
     u64* dst = b;
     for (int g = 0; g < k; ++g) {
         i64 ext = k - 1 - g;
-        step_rows(src, dst, L, -ext, L.h + ext);
+        step_rows(src, dst, L, -ext, L.h + ext, rule);
         std::swap(src, dst);
     }
     return src;

@@ -21,6 +21,17 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     : g_(g), cfg_(c), t_(std::move(t)) {
     if (!t_) throw Error("engine needs a transport");
     xchg_self_ = cfg_.self_exchange && !cfg_.compat;
+    Rule::from_masks(cfg_.rule.birth, cfg_.rule.survive);  // (a rule set by its masks: range and B0 checks)
+    if (!cfg_.rule.is_conway()) {
+        const std::string rs = cfg_.rule.str();
+        if (cfg_.compat) throw Error("GOL_COMPAT=reference with rule " + rs + ": the reference has one rule, B3/S23");
+        if (cfg_.subtiles == 2) throw Error("two sub-tiles per rank (GOL_SUBTILES=2) run B3/S23 only, not rule " + rs);
+        if (cfg_.backend == "hip")
+            for (const char* k : {"temporal", "tile", "pipe", "resident", "lds"})
+                if (cfg_.kernel == k)
+                    throw Error("kernel '" + cfg_.kernel + "' implements B3/S23 only, not rule " + rs +
+                                " (use kernel auto or rule)");
+    }
     if (t_->size() != g_.dec.P || t_->rank() != g_.rank)
         throw Error(strprintf("transport (rank %d of %d) does not match the geometry (rank %d of %d)", t_->rank(),
                               t_->size(), g_.rank, g_.dec.P));
@@ -47,7 +58,8 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     // 9.70-9.79 at 128 (profiles/subtile_superstep_boundaries.txt).  Rank-invariant inputs only.
     const bool sub_tall = cfg_.backend == "hip" && (cfg_.subtiles == 2 || cfg_.subtiles < 0) && !two_d() && strip_rows >= kSubtileMinRows &&
                           g_.dec.W % 64 == 0 && !cfg_.force_split && !cfg_.profile && !cfg_.compat &&
-                          cfg_.kernel != "lds" && cfg_.kernel != "tile" && cfg_.kernel != "pipe";
+                          cfg_.kernel != "lds" && cfg_.kernel != "tile" && cfg_.kernel != "pipe" &&
+                          cfg_.kernel != "rule" && cfg_.rule.is_conway();
     // (1-D strips with neighbours: 128 measured 1-3% faster than 64 through RCCL self-exchange,
     // 4096 x 32768 2.44 -> 2.36, 8192 x 65536 5.93 -> 5.85 us/gen; profiles/per_rank_tiles_self_exchange.txt)
     const int want = cfg_.halo_depth > 0 ? cfg_.halo_depth : (sub_tall || tall_strips ? 128 : (tall_tiles ? 56 : 32));
@@ -59,6 +71,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     }
     L_ = Layout(g_.h, g_.w, R);
     stats_.depth = R;
+    stats_.rule = cfg_.rule.str();
     std::string f = env_str("GOL_FAULT", "");
     if (!f.empty()) {
         int fr = -1;
@@ -111,10 +124,10 @@ std::unique_ptr<Engine> Engine::create(const Geometry& g, const EngineConfig& c,
 
 std::string Engine::describe() const {
     const std::string wg = cfg_.backend == "hip" ? strprintf(", tile workgroup %d waves", cfg_.tile_waves) : "";
-    return strprintf("%s backend, %s, rank %d tile %lldx%lld at (%lld,%lld), halo depth %d, transport %s%s%s",
+    return strprintf("%s backend, %s, rank %d tile %lldx%lld at (%lld,%lld), halo depth %d, transport %s%s%s, rule %s",
                      backend_name().c_str(), g_.dec.describe().c_str(), g_.rank, (long long)g_.h, (long long)g_.w,
                      (long long)g_.row0, (long long)g_.col0, L_.R, t_->name().c_str(), wg.c_str(),
-                     cfg_.compat ? ", compat=reference" : "");
+                     cfg_.compat ? ", compat=reference" : "", cfg_.rule.str().c_str());
 }
 
 std::vector<Engine::HaloItem> Engine::halo_items(int k) const {
@@ -156,6 +169,16 @@ void Engine::init(const PatternSpec& p) {
     stats_.kernel = backend_name() == "cpu" ? "cpu" : cfg_.kernel;
     stats_.schedule = halo_items(L_.R).empty() ? "local" : "full";
     stats_.kernel_depth = L_.R;
+    stats_.rule = cfg_.rule.str();
+    if (t_->size() > 1) {
+        // every rank must run the same rule: agreed like the schedule, by reductions every rank sees
+        // (so on a mismatch every rank raises and none waits for a peer)
+        const double code = (double)cfg_.rule.code();
+        const double lo = t_->allreduce_min(code), hi = t_->allreduce_max(code);
+        if (lo != hi)
+            throw Error(strprintf("the ranks disagree on the rule: rank %d has %s (rule codes 0x%x .. 0x%x over the ranks)",
+                                  g_.rank, stats_.rule.c_str(), (unsigned)lo, (unsigned)hi));
+    }
     do_init(p);
     if (cfg_.compat) setup_compat();
     if (wd_) wd_->enable_probe();
@@ -313,7 +336,7 @@ class CpuEngine : public Engine {
             exchange(k);
             if (self_y()) cpu::fill_ghost_rows_wrap(cur_, L_);
         }
-        u64* res = cpu::superstep(cur_, oth_, L_, k);
+        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule);
         if (res != cur_) std::swap(cur_, oth_);
         if (self_x()) cpu::fill_ghost_cols_wrap(cur_, L_, 0, L_.h);
     }

@@ -38,6 +38,10 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
     cus_ = prop.multiProcessorCount;
     int R = L_.R;
     kernel_ = cfg_.kernel;
+    // A non-Conway rule, or kernel "rule" (B3/S23 through the generic kernel: its cross-check), runs step_rule
+    // in every pass of every plan kind.  (Engine::Engine refused the specialised kernels with such a rule.)
+    rule_ = kernel_ == "rule" || !cfg_.rule.is_conway();
+    if (rule_ && kernel_ == "auto") kernel_ = "rule";  // (any other name is refused below)
     hipk::ensure_trash();  // before any launch or graph capture
     // Kernel pass depth K (generations per HBM pass) vs halo depth R (generations per
     // exchange).  In 1-D (and on a single rank) a superstep of R generations runs as several
@@ -52,6 +56,8 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
         R = K = 1;
     } else if (kernel_ == "tile") {
         K = std::min(K, 32);  // any depth; LDS rows bound it (tile_max_rows)
+    } else if (kernel_ == "rule") {
+        K = supported_kernel_depth(std::min(K, max_depth()));
     } else if (kernel_ == "temporal" || kernel_ == "auto" || kernel_ == "resident") {
         // auto: the depth must suit both candidates (instantiated temporal depths)
         K = supported_kernel_depth(std::min(K, hipk::max_step_depth()));
@@ -66,7 +72,7 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
             throw Error(strprintf("GOL_KERNEL=pipe: its pass depth %d exceeds the halo depth %d (GOL_HALO_DEPTH)", pipe_k_, R));
         K = pipe_k_;
     } else {
-        throw Error("GOL_KERNEL must be auto, temporal, tile, pipe, lds or resident (got '" + kernel_ + "')");
+        throw Error("GOL_KERNEL must be auto, temporal, tile, pipe, lds, resident or rule (got '" + kernel_ + "')");
     }
     if (!multipass_) R = std::min(R, K);
     kdepth_ = K;
@@ -315,7 +321,11 @@ void HipEngine::do_init(const PatternSpec& p) {
             if (wd_) wd_->kick(phase);
         };
         kick("init: kernel autotune");
-        if (cfg_.kernel == "auto" || cfg_.kernel == "resident") autotune_kernel();
+        if (rule_) {
+            if (cfg_.kernel == "auto") autotune_rule();
+        } else if (cfg_.kernel == "auto" || cfg_.kernel == "resident") {
+            autotune_kernel();
+        }
         // The one-tile pass costs first: the schedule candidates are timed on the pass cuts the runs
         // will use (config 3's strip: one step_pipe pass of 20 instead of 7 + 7 + 6 changed the winner)
         kick("init: pass costs");
@@ -342,6 +352,10 @@ void HipEngine::finish_init() {
     stats_.kernel = split_ ? kern_[1] + "+boundary:" + kern_[2] : (dual_ ? std::string("temporal") : kern_[0]);
     if (!split_ && !dual_ && kern_[0] == "pipe")
         stats_.kernel = strprintf("pipe@%d(%dx%d,%d/CU)", pipe_k_, pipe_cur_.nw - 1, pipe_cur_.l, pipe_cur_.wg);
+    if (rule_) {
+        const std::string rk = strprintf("rule@%d", kdepth_);
+        stats_.kernel = split_ ? rk + "+boundary:" + rk : rk;
+    }
     if (res_) {
         const ResPlan& rp = res_plan(res_kin_);
         stats_.kernel = strprintf("resident@%d(%lld tiles x %d waves x %d rows)", res_kin_, (long long)rp.tiles, rp.nw, rp.B);
@@ -366,6 +380,7 @@ void HipEngine::finish_init() {
                 const PassKernel pk = pass_kernel(kind, ps[j]);
                 c += (j ? "+" : "") + (pk == PK_PIPE   ? strprintf("pipe@%d(%dx%d,%d/CU)", ps[j], g->nw - 1, g->l, g->wg)
                                        : pk == PK_TILE ? strprintf("tile@%d", ps[j])
+                                       : pk == PK_RULE ? strprintf("rule@%d", ps[j])
                                                        : strprintf("temporal@%d", ps[j]));
             }
             tn += strprintf("%scut%d=%s", tn.empty() ? "" : " ", k, c.c_str());
@@ -596,6 +611,8 @@ void HipEngine::launch(int kind, int k, i64 e, const u64* src, u64* dst, hipStre
             const PipeGeo* g = pipe_geo(k);
             hipk::launch_step_pipe(g->nw, g->l, src, dst, p.d, p.waves, sp, s);
             pipe_used_ = true;
+        } else if (pk == PK_RULE) {
+            hipk::launch_step_rule(k, cfg_.rule, src, dst, p.d, p.waves, sp, s);
         } else
             hipk::launch_step(k, src, dst, p.d, p.waves, sp, s);
     }

@@ -18,7 +18,7 @@ const std::vector<int>& HipEngine::pass_depths(int k) {
     // every kind may be temporal, unless only the (any-depth) tile kernel runs; sub-tiles always
     // run the temporal kernel at its own depth
     const bool any_depth = !dual_ && (cfg_.kernel == "tile" || (tuned_ && !split_ && tile_kernel(0)));
-    auto ok = [&](int d) { return any_depth || hipk::step_depth_supported(d); };
+    auto ok = [&](int d) { return any_depth || depth_ok(d); };
     const int K = std::max(1, dual_ ? tdepth_ : kdepth_);
     std::vector<int> ps;
     if (!pass_costs().empty() && !any_depth) {
@@ -39,7 +39,7 @@ const std::vector<int>& HipEngine::pass_depths(int k) {
             bool okd = true;
             for (int j = 0; j < n; ++j) {
                 const int d = left / n + (j < left % n ? 1 : 0);
-                okd = okd && hipk::step_depth_supported(d);
+                okd = okd && depth_ok(d);
                 v.push_back(d);
             }
             if (!okd) {
@@ -175,7 +175,7 @@ const DevPlan& HipEngine::plan(int kind, int k, i64 e) {
             rows = choose_rows_per_chunk(rg, k, cfg_.waves_target, 4 * (i64)k);
         if (rows <= 0) {
             // one full round of resident waves (occupancy of this kernel instantiation)
-            i64 bpc = hipk::step_blocks_per_cu(k, step_flags());
+            i64 bpc = blocks_per_cu(k, step_flags());
             // 256-thread blocks per CU = waves per SIMD; the tuned cap applies to the tuned depth
             // only (shallower passes are memory bound and want every resident wave)
             if (occ_ > 0 && k == kdepth_) bpc = std::min<i64>(bpc, occ_);

@@ -22,7 +22,7 @@ void HipEngine::spin_up() {
         if (cfg_.kernel != "tile") kern_[0] = "temporal";  // the register kernel runs on any board
         // (sub-tiles: their own pass depth; a deep full-tile depth, e.g. a pipe candidate's 36, would
         // spin the GPU up on a 1-wave-per-SIMD kernel of a different power draw)
-        k = tile_kernel(0) ? kdepth_ : supported_kernel_depth(std::min(dual_ ? tdepth_ : kdepth_, hipk::max_step_depth()));
+        k = tile_kernel(0) ? kdepth_ : supported_kernel_depth(std::min(dual_ ? tdepth_ : kdepth_, max_depth()));
     }
     const auto t0 = std::chrono::steady_clock::now();
     for (int it = 0; it < 100000; ++it) {
@@ -49,14 +49,14 @@ void HipEngine::measure_pass_costs() {
     // 20-generation superstep cut 12 + 8 measured cheaper than 8 + 8 + 4 (the K=12 pass runs 2 waves
     // per SIMD at ~10.6 us/gen as two halves, vs 10.3 at K=8; profiles/pingpong_loop_ab.txt)
     const int K = dual_ ? tdepth_ : kdepth_;
-    const int kmax = std::min(superstep_depth(), hipk::max_step_depth());
+    const int kmax = std::min(superstep_depth(), max_depth());
     struct Cand {
         int d;
         PipeGeo g;  // g.nw > 0: a step_pipe pass of this geometry
     };
     std::vector<Cand> cs;
     for (int d = 1; d <= std::max(K, kmax); ++d)
-        if (hipk::step_depth_supported(d)) cs.push_back({d, {}});
+        if (depth_ok(d)) cs.push_back({d, {}});
     // A one tile whose tuned kernel is step_pipe: its passes may be step_pipe at any depth one of these
     // geometries reaches (and the superstep allows), so a superstep is cut into the cheapest mix, e.g.
     // the driver's 20-generation run on config 3's 4096 x 32768 strip as ONE step_pipe pass of 20
@@ -502,7 +502,7 @@ void HipEngine::time_schedule(const std::string& c, int k, int reps, bool eager)
 // latency-bound: 10 stages x 2 generations stream a 60-row segment, where the tile kernel runs 20
 // generations of barriers, 38 us for a 20-row band of config 3's strip; profiles/strip_split_round5.txt).
 void HipEngine::tune_split_kinds(int k) {
-    if (cfg_.kernel != "auto" && cfg_.kernel != "resident") return;
+    if (rule_ || (cfg_.kernel != "auto" && cfg_.kernel != "resident")) return;
     std::vector<const char*> cands = {"temporal", "tile"};
     if (kern_[0] == "pipe") cands.push_back("pipe");
     hipEvent_t e0, e1;
@@ -742,6 +742,43 @@ void HipEngine::autotune_kernel() {
     } else if (cfg_.kernel == "resident") {
         throw Error("GOL_KERNEL=resident needs a rank without neighbours, a 1-D tile of width % 64 == 0 and >= 64 rows");
     }
+}
+
+// Under a rule the only kernel is step_rule, so `auto` tunes what still applies: the occupancy the one-round
+// plans are sized for (full, or 2 waves per SIMD: fewer, taller waves pay less vertical halo), at the pass
+// depth.  The pass depths of a superstep come from measure_pass_costs, as for step_temporal.
+void HipEngine::autotune_rule() {
+    const int k0 = kdepth_;
+    if (cfg_.rows_per_wave > 0 || cfg_.waves_target > 0 || blocks_per_cu(k0, step_flags()) <= 2) return;
+    hipEvent_t e0, e1;
+    HIP_CHECK(hipEventCreate(&e0));
+    HIP_CHECK(hipEventCreate(&e1));
+    const int occs[2] = {0, 2};
+    for (int o : occs) {  // every plan first (plan building idles the GPU)
+        occ_ = o;
+        plan(0, k0, 0);
+    }
+    spin_up();
+    float best[2] = {1e30f, 1e30f};
+    for (int round = 0; round < 3; ++round)
+        for (int c = 0; c < 2; ++c) {
+            occ_ = occs[c];
+            launch(0, k0, 0, buf_[cur_], buf_[cur_ ^ 1], s_comp_);  // warm-up
+            HIP_CHECK(hipEventRecord(e0, s_comp_));
+            for (int i = 0; i < 3; ++i) launch(0, k0, 0, buf_[cur_], buf_[cur_ ^ 1], s_comp_);
+            HIP_CHECK(hipEventRecord(e1, s_comp_));
+            HIP_CHECK(hipEventSynchronize(e1));
+            float ms = 0;
+            HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+            const float per_gen = ms / 3 / (float)k0;
+            init_step("init: kernel autotune", "rule", k0, per_gen * 1e3f);
+            best[c] = std::min(best[c], per_gen);
+            tune_ms_[occs[c] ? strprintf("0:rule@%d/%dw", k0, occs[c]) : strprintf("0:rule@%d", k0)] = best[c];
+        }
+    occ_ = best[1] < best[0] ? occs[1] : occs[0];
+    HIP_CHECK(hipEventDestroy(e0));
+    HIP_CHECK(hipEventDestroy(e1));
+    passes_.clear();
 }
 
 void HipEngine::device_barrier() {

@@ -177,7 +177,7 @@ class HipEngine : public Engine {
     bool dual_wanted() const {
         const bool want = cfg_.subtiles == 2 ||
                           (cfg_.subtiles < 0 && g_.dec.H / std::max(1, g_.dec.Py) >= kSubtileMinRows && L_.R >= 64);
-        return want && !two_d() && !cfg_.compat && !cfg_.profile && !cfg_.force_split && L_.aligned() &&
+        return want && !rule_ && !two_d() && !cfg_.compat && !cfg_.profile && !cfg_.force_split && L_.aligned() &&
                cfg_.kernel != "lds" && cfg_.kernel != "tile" && cfg_.kernel != "pipe";
     }
     // Rank-local conditions (agreed over the ranks by the caller): a tile tall enough for two
@@ -295,8 +295,14 @@ class HipEngine : public Engine {
         for (size_t i = j + 1; i < ps.size(); ++i) e += ps[i];
         return e;
     }
-    static int supported_kernel_depth(int want) {
-        while (want > 1 && !hipk::step_depth_supported(want)) --want;
+    // The streaming kernel of this engine: step_rule under a rule (rule_), else step_temporal.
+    bool depth_ok(int k) const { return rule_ ? hipk::rule_depth_supported(k) : hipk::step_depth_supported(k); }
+    int max_depth() const { return rule_ ? hipk::max_rule_depth() : hipk::max_step_depth(); }
+    int blocks_per_cu(int k, u32 flags) const {
+        return rule_ ? hipk::rule_blocks_per_cu(k, flags) : hipk::step_blocks_per_cu(k, flags);
+    }
+    int supported_kernel_depth(int want) const {
+        while (want > 1 && !depth_ok(want)) --want;
         return std::max(1, want);
     }
 
@@ -421,8 +427,10 @@ class HipEngine : public Engine {
     // that kind's tuned kernel is step_pipe (the interior of a split first pass too, when the full tile's
     // is) and a geometry of depth k exists; else step_temporal where it is instantiated, else the tile
     // kernel (any depth: the bands of a first pass at a step_pipe depth).
-    enum PassKernel { PK_TEMPORAL, PK_TILE, PK_PIPE };
+    // Under a rule (rule_: a non-Conway rule, or kernel "rule") every pass of every kind is step_rule.
+    enum PassKernel { PK_TEMPORAL, PK_TILE, PK_PIPE, PK_RULE };
     PassKernel pass_kernel(int kind, int k) const {
+        if (rule_) return PK_RULE;
         if (kern_[kind] == "tile") return PK_TILE;
         // (an interior explicitly tuned to step_temporal keeps it: tune_split_kinds times it as such)
         if ((kern_[kind] == "pipe" || (kind == 1 && kern_[0] == "pipe" && kern_[1] != "temporal")) && pipe_geo(k))
@@ -453,6 +461,7 @@ class HipEngine : public Engine {
     }
 
     void autotune_kernel();
+    void autotune_rule();  // under a rule: only the plan occupancy (the pass depths: measure_pass_costs)
     void tune_split_kinds(int k);
 
     bool can_overlap() const {
@@ -535,7 +544,7 @@ class HipEngine : public Engine {
         i64 rows = 0;
     };
     bool resident_eligible() const {
-        return halo_items(L_.R).empty() && !two_d() && self_y() && xwrap_by_plan() && !cfg_.compat && !cfg_.profile &&
+        return !rule_ && halo_items(L_.R).empty() && !two_d() && self_y() && xwrap_by_plan() && !cfg_.compat && !cfg_.profile &&
                !cfg_.force_split && L_.h >= 64;
     }
     const ResPlan& res_plan(int kin);
@@ -573,7 +582,8 @@ class HipEngine : public Engine {
     Watchdog::Probe probe() override;
 
     int dev_ = 0, cus_ = 256;
-    std::string kernel_;  // resolved kernel: temporal | tile | lds (auto resolves at init)
+    std::string kernel_;  // resolved kernel: temporal | tile | lds | rule (auto resolves at init)
+    bool rule_ = false;   // the generic kernel step_rule runs every pass (a non-Conway rule, or kernel "rule")
     std::string kern_[3];  // per plan kind (full / interior / boundary), resolved by autotune
     int kdepth_ = 8;       // kernel pass depth K (<= halo depth R)
     int tdepth_ = 8;       // temporal-kernel pass depth (the sub-tile mode's, whatever kernel one tile uses)

@@ -165,6 +165,7 @@ EngineConfig engine_config(const Options& o, const std::string& backend, int dev
     c.rows_per_wave = o.rows_per_wave;
     c.waves_target = o.waves_target;
     c.kernel = env_str("GOL_KERNEL", "auto");
+    c.rule = Rule::parse(env_str("GOL_RULE", "B3/S23"));
     c.tile_waves = (int)env_int("GOL_TILE_WAVES", 8);
     c.tune_tile_waves = getenv("GOL_TILE_WAVES") == nullptr;
     c.transport = (o.transport == "rccl" || o.transport == "p2p") ? "device" : o.transport;
@@ -316,6 +317,7 @@ void save_checkpoint(Engine& eng, const std::string& prefix, u64 seed) {
         hd.words_per_row = (u64)gw;
         hd.generation = eng.generation();
         hd.seed = seed;
+        hd.reserved[0] = eng.config().rule.code();  // birth | survive << 16 (0, older files: B3/S23)
         const int fd = open(tmp.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
         ok = fd >= 0 && ftruncate(fd, (off_t)(sizeof(hd) + (size_t)(g.dec.H * gw) * 8)) == 0 &&
              pwrite(fd, &hd, sizeof(hd), 0) == (ssize_t)sizeof(hd);
@@ -371,6 +373,14 @@ u64 load_checkpoint(Engine& eng, const std::string& prefix) {
             throw Error(strprintf("checkpoint %s holds a %llux%llu board, this run has %lldx%lld", name.c_str(),
                                   (unsigned long long)hd.H, (unsigned long long)hd.W, (long long)g.dec.H,
                                   (long long)g.dec.W));
+        // (every rank reads the header: a rule mismatch raises on all of them, before anything collective)
+        const Rule mine = eng.config().rule;
+        const u64 code = hd.reserved[0] ? hd.reserved[0] : Rule().code();
+        if (code != mine.code()) {
+            const Rule theirs = Rule::from_masks((unsigned)(code & 0xFFFFu), (unsigned)((code >> 16) & 0xFFFFu));
+            throw Error("checkpoint " + name + " was written under rule " + theirs.str() + ", this run has " +
+                        mine.str());
+        }
         std::vector<u64> words((size_t)(g.h * nw));
         const off_t base = (off_t)sizeof(CkptHeader);
         if (nw == gw) {
@@ -424,6 +434,7 @@ void write_metrics(const Options& o, Engine& eng, const CliArgs& a, double durat
     f << "  \"halo_bytes_rank0\": " << s.halo_bytes << ",\n";
     f << "  \"graph_launches\": " << s.graph_launches << ",\n";
     f << "  \"kernel\": \"" << s.kernel << "\",\n";
+    f << "  \"rule\": \"" << s.rule << "\",\n";
     f << "  \"schedule\": \"" << s.schedule << "\",\n";
     f << "  \"autotune\": \"" << s.tuning << "\",\n";
     f << "  \"plan_waves\": " << s.plan_waves << ",\n  \"lane_efficiency\": " << s.lane_efficiency << ",\n";
@@ -523,6 +534,9 @@ int run_cli(int argc, char** argv) {
     }
     try {
         Options o = options_from_env();
+        // GOL_RULE (read again per rank in engine_config, beside GOL_KERNEL): a bad value ends the job here,
+        // with the parse error, before any rank starts
+        (void)Rule::parse(env_str("GOL_RULE", "B3/S23"));  // (GOL_VERBOSE=1: describe() names the rule)
         LaunchInfo li = detect_launch(o);
         if (li.mode == "threads") {
             auto group = make_thread_group(li.size);

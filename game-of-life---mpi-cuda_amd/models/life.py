@@ -45,13 +45,17 @@ class Simulation:
     halo_depth:   generations per halo exchange (<= 128 in 1-D, <= 63 in 2-D; 0 = auto, as in
                   Engine::Engine: 128 for 1-D strips of >= 2048 rows with neighbours (or the
                   self-exchange) and for ranks that can run two sub-tiles, 56 for 2-D tiles of >= 2048
-                  rows with neighbours, otherwise 32).  The rule is B3/S23 (Conway), the only rule
-                  the bit-sliced kernels implement.
+                  rows with neighbours, otherwise 32).
+    rule:         the life-like rule, ``"B36/S23"`` or an alias (conway, life, highlife, daynight, seeds,
+                  replicator); default B3/S23 (GOL_RULE).  B3/S23 runs the specialised bit-sliced kernels;
+                  any other B0-free rule the generic ones (HIP: ``step_rule``, CPU: a bit-sliced count),
+                  without ``compat``, ``subtiles=2`` or the B3/S23-only kernels.
     kernel_depth: generations per kernel pass (HIP; 0 = auto).  A superstep of halo_depth
                   generations runs as several kernel passes in 1-D (communication-avoiding halos).
     kernel:       HIP stencil kernel: ``"auto"`` (candidates timed at init), ``"temporal"``,
                   ``"tile"``, ``"pipe"`` (level-pipelined workgroups; geometry GOL_PIPE=nw,L,wg),
-                  ``"resident"`` or ``"lds"`` (GOL_KERNEL).
+                  ``"resident"``, ``"lds"`` or ``"rule"`` (the generic rule kernel, also for B3/S23;
+                  GOL_KERNEL).
     decomp/grid:  ``"1d"`` row strips (reference) or ``"2d"`` blocks, optional ``"PxxPy"`` grid.
     width:        board columns (0 = N: the reference's square tiles).  With ``width`` the per-rank
                   strip (or, in global mode, the board) is N rows x ``width`` columns.
@@ -88,6 +92,7 @@ class Simulation:
         subtiles: int = -1 if os.environ.get("GOL_SUBTILES", "auto") == "auto" else int(os.environ["GOL_SUBTILES"]),
         width: int = 0,
         subtile_overlap: Optional[int] = None,
+        rule: str = os.environ.get("GOL_RULE", "B3/S23"),
     ):
         self.transport = transport if transport is not None else _gol.SelfTransport()
         P, rank = self.transport.size(), self.transport.rank()
@@ -102,6 +107,14 @@ class Simulation:
         cfg.graph = graph
         cfg.compat = compat
         cfg.kernel = kernel
+        cfg.rule = rule  # (ValueError on a string that is no B0-free rule)
+        if cfg.rule != "B3/S23":
+            if compat:
+                raise ValueError(f"compat=True with rule {cfg.rule}: the reference has one rule, B3/S23")
+            if int(subtiles) == 2:
+                raise ValueError(f"subtiles=2 runs B3/S23 only, not rule {cfg.rule}")
+            if self.backend == "hip" and kernel in ("temporal", "tile", "pipe", "resident", "lds"):
+                raise ValueError(f"kernel {kernel!r} implements B3/S23 only, not rule {cfg.rule}")
         cfg.subtiles = int(subtiles)  # 2 / 0 / -1 auto: two sub-tiles per rank on two streams (HIP, 1-D)
         cfg.run_hint = int(run_hint)  # generations of the runs to come: one replay graph covers them
         cfg.rows_per_wave = rows_per_wave

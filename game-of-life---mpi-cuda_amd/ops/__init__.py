@@ -1,7 +1,17 @@
 """Ops: bit packing, oracles (numpy / torch conv2d / reference-quirk model) and direct access to the
 native kernels through the ``_gol`` extension."""
 from .bitpack import pack_cells, unpack_words  # noqa: F401
-from .oracle import initial_board, numpy_step, quirk_model, random_board, torch_step  # noqa: F401
+from .oracle import (  # noqa: F401
+    initial_board,
+    numpy_step,
+    numpy_step_rule,
+    parse_rule,
+    quirk_model,
+    random_board,
+    rule_string,
+    torch_step,
+    torch_step_rule,
+)
 from .._native import _gol as _native
 
 

@@ -3,6 +3,8 @@
 * :func:`numpy_step` — byte-per-cell torus step (numpy roll), the plain reference.
 * :func:`torch_step` — the same with a 3x3 ``conv2d`` and circular padding in fp32; runs on the GPU
   (PyTorch-ROCm) to cross-check large boards independently of the HIP kernels.
+* :func:`numpy_step_rule` / :func:`torch_step_rule` — the same two for any life-like rule ``B.../S...``,
+  with a rule parser of their own (independent of the native one).
 * :func:`quirk_model` — the reference's actual behaviour (survey Q1-Q3): every rank steps its tile
   with x-wrap and CONSTANT ghost rows taken from the generation-0 boards, with the P <= 2 swap.
 * :func:`initial_board` — pattern placement mirror (patterns 0-5) computed in Python, including the
@@ -42,6 +44,86 @@ def torch_step(board, generations: int = 1, device=None):
     for _ in range(generations):
         n = F.conv2d(F.pad(x, (1, 1, 1, 1), mode="circular"), k)
         x = ((n == 3) | ((x == 1) & (n == 2))).to(torch.float32)
+    return x[0, 0].to(torch.uint8)
+
+
+_RULE_ALIASES = {
+    "conway": "b3/s23",
+    "life": "b3/s23",
+    "highlife": "b36/s23",
+    "daynight": "b3678/s34678",
+    "seeds": "b2/s",
+    "replicator": "b1357/s1357",
+}
+
+
+def parse_rule(rule) -> tuple:
+    """A rule as ``(birth, survive)`` masks: bit c of birth / survive = a dead / live cell with c live
+    neighbours is alive next generation.  Takes ``"B36/S23"`` (either order, either case, empty digit
+    lists allowed), an alias (conway, life, highlife, daynight, seeds, replicator) or a mask pair.
+    B0 rules are refused, as in the engine."""
+    if not isinstance(rule, str):
+        birth, survive = (int(v) for v in rule)
+        if not (0 <= birth < 512 and 0 <= survive < 512):
+            raise ValueError(f"invalid rule {rule!r}: masks have bits 0..8")
+    else:
+        text = _RULE_ALIASES.get(rule.lower(), rule.lower())
+        parts = text.split("/")
+        if len(parts) != 2 or {p[:1] for p in parts} != {"b", "s"}:
+            raise ValueError(f"invalid rule {rule!r}: expected B<digits>/S<digits>")
+        masks = {}
+        for p in parts:
+            digits = p[1:]
+            if not all(c in "012345678" for c in digits) or len(set(digits)) != len(digits):
+                raise ValueError(f"invalid rule {rule!r}: digits are 0..8, each at most once")
+            masks[p[0]] = sum(1 << int(c) for c in digits)
+        birth, survive = masks["b"], masks["s"]
+    if birth & 1:
+        raise ValueError(f"invalid rule {rule!r}: B0 rules are out of scope (the dead background would come alive)")
+    return birth, survive
+
+
+def rule_string(rule) -> str:
+    """Canonical ``B<digits>/S<digits>`` (digits ascending)."""
+    birth, survive = parse_rule(rule)
+    digits = lambda m: "".join(str(c) for c in range(9) if (m >> c) & 1)  # noqa: E731
+    return f"B{digits(birth)}/S{digits(survive)}"
+
+
+def numpy_step_rule(board: np.ndarray, rule, generations: int = 1) -> np.ndarray:
+    """Byte-per-cell torus step of a life-like rule (string or ``(birth, survive)`` pair)."""
+    birth, survive = parse_rule(rule)
+    lut = np.array([[(birth >> c) & 1 for c in range(9)], [(survive >> c) & 1 for c in range(9)]], dtype=np.uint8)
+    b = np.asarray(board, dtype=np.uint8)
+    for _ in range(generations):
+        n = sum(
+            np.roll(np.roll(b, dy, axis=0), dx, axis=1)
+            for dy in (-1, 0, 1)
+            for dx in (-1, 0, 1)
+            if dy or dx
+        )
+        b = lut[b, n]
+    return b
+
+
+def torch_step_rule(board, rule, generations: int = 1, device=None):
+    """A life-like rule on a torus with torch conv2d (fp32, exact for counts <= 8).  Returns a torch uint8 tensor."""
+    import torch
+    import torch.nn.functional as F
+
+    birth, survive = parse_rule(rule)
+    if isinstance(board, torch.Tensor):
+        x = board.to(device=device if device is not None else board.device, dtype=torch.float32)[None, None]
+    else:
+        x = torch.as_tensor(np.asarray(board), dtype=torch.float32, device=device)[None, None]
+    k = torch.ones(1, 1, 3, 3, dtype=torch.float32, device=x.device)
+    k[0, 0, 1, 1] = 0
+    lut = torch.tensor(
+        [(birth >> c) & 1 for c in range(9)] + [(survive >> c) & 1 for c in range(9)], dtype=torch.float32, device=x.device
+    )
+    for _ in range(generations):
+        n = F.conv2d(F.pad(x, (1, 1, 1, 1), mode="circular"), k)
+        x = lut[(x * 9 + n).to(torch.int64)]
     return x[0, 0].to(torch.uint8)
 
 
