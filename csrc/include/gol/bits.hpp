@@ -183,6 +183,24 @@ BITS_HD void wrap_row_ghosts(u64* row, i64 w, i64 nw) {
     row[nw] = split_word(right);
 }
 
+// Stamping a pattern (stamp(), engine.hpp): board word `cw` (split storage) of a tile row whose columns
+// [tc, tc + cols) take the bits of the pattern row `prow` (natural-order words) from its column pc0 on.
+// mode: 0 or, 1 replace (the rectangle's columns are overwritten), 2 xor, 3 clear (dead where the pattern is
+// live).  Bits of the word outside the rectangle stay as they are.  The caller passes words the rectangle touches.
+BITS_HD u64 stamp_word(u64 word, const u64* prow, i64 pc0, i64 tc, i64 cols, i64 cw, int mode) {
+    const i64 lo = tc > 64 * cw ? tc : 64 * cw;
+    const i64 hi = tc + cols < 64 * cw + 64 ? tc + cols : 64 * cw + 64;
+    const int n = (int)(hi - lo), sh = (int)(lo & 63);
+    const u64 pat = split_word(extract_bits(prow, pc0 + (lo - tc), n) << sh);
+    const u64 mask = split_word((n >= 64 ? ~0ull : ((1ull << n) - 1ull)) << sh);
+    switch (mode) {
+        case 0: return word | pat;
+        case 1: return (word & ~mask) | pat;
+        case 2: return word ^ pat;
+        default: return word & ~pat;
+    }
+}
+
 // Fingerprint contribution of one (masked) word at global word index `gidx`.  The fingerprint is
 // the wrapping sum over all words, so it is independent of how the board is split across ranks.
 BITS_HD u64 fingerprint_word(u64 gidx, u64 word) { return word ? mix64(mix64(gidx) ^ word) : 0ull; }

@@ -51,6 +51,10 @@ struct Options {
     std::string restart = "";       // GOL_RESTART   snapshot prefix to resume from
     double watchdog_s = 0;          // GOL_WATCHDOG  seconds before a stuck exchange aborts (0 = off)
     bool verbose = false;           // GOL_VERBOSE   log configuration to stderr
+    std::string pattern_file = "";  // GOL_PATTERN_FILE RLE file stamped (or mode) after the positional pattern's init
+    std::string pattern_at = "";    // GOL_PATTERN_AT  row,col of the file's first cell (default: centred)
+    std::string rle_out = "";       // GOL_RLE_OUT   rank 0 writes the final global board as RLE (<= 2^26 cells)
+    std::string rule = "";          // the run's rule when GOL_PATTERN_FILE names one and GOL_RULE is unset
 };
 
 Options options_from_env();

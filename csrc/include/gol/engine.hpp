@@ -26,6 +26,7 @@
 #include "gol/geometry.hpp"
 #include "gol/pattern.hpp"
 #include "gol/plan.hpp"
+#include "gol/rle.hpp"
 #include "gol/rule.hpp"
 #include "gol/transport.hpp"
 #include "gol/watchdog.hpp"
@@ -103,7 +104,13 @@ struct EngineStats {
     std::string schedule;      // superstep schedule: local (no neighbours) | split | full
     std::string tuning;        // init-time measurements behind the auto choices (HIP)
     bool registered = false;   // HIP + RCCL: the boards are registered with the communicator (zero-copy halos)
+    u64 view_bytes_d2h = 0;    // HIP: bytes window() copied from the device (this rank's cells of the windows)
 };
+
+// How stamp() combines a pattern with the board.  Replace overwrites the pattern's bounding rectangle;
+// Clear kills the cells where the pattern is live.
+enum class StampMode : int { Or = 0, Replace, Xor, Clear };
+StampMode parse_stamp_mode(const std::string& s);  // or | replace | xor | clear
 
 class Engine {
    public:
@@ -124,6 +131,37 @@ class Engine {
     // Global values (collective over the transport).
     u64 population();
     u64 fingerprint();
+
+    // ----- views and pattern stamping -----
+    // Global board coordinates on the torus: a window or a pattern may start anywhere (r0, c0 are taken
+    // modulo the board), cross the board's seams and any rank boundary; it is at most the board's size.
+    // The *_local virtuals do this rank's part, the wrappers below them are collective and return the
+    // whole result on every rank (the parts travel over the control plane: gatherv to rank 0, broadcast).
+    // Arguments are validated before any communication: a bad call throws on every rank, none hangs.
+    //
+    // This rank's cells of the window as 0/1 bytes at out[i * stride + j]; other ranks' cells are untouched.
+    virtual void read_window_local(i64 r0, i64 c0, i64 rows, i64 cols, u8* out, i64 stride) = 0;
+    // Adds the live-cell counts of this rank's cells into a ceil(H / block_rows) x ceil(W / block_cols) grid
+    // over the global board (edge blocks are partial).  block_cols is a multiple of 64.
+    virtual void density_local(i64 block_rows, i64 block_cols, u32* counts) = 0;
+    // Combines this rank's cells of the pattern's rectangle at (r0, c0) with the board; ghosts and halos are
+    // brought up to date as set_tile_words does.  Refused for a pattern larger than the board (it would
+    // overlap itself) and in compat mode (its halos are frozen at generation 0).
+    virtual void stamp_local(const RlePattern& p, i64 r0, i64 c0, StampMode mode) = 0;
+    std::vector<u8> window(i64 r0, i64 c0, i64 rows, i64 cols);     // rows x cols bytes
+    std::vector<u32> density(i64 block_rows, i64 block_cols);        // density_rows() x density_cols()
+    void stamp(const RlePattern& p, i64 r0, i64 c0, StampMode mode);  // (no communication: every rank holds p)
+    // The part of the wrapped global rectangle (r0, c0, rows, cols) inside the tile of geometry g: at most
+    // four pieces (the rectangle is cut where it crosses the board's seams).
+    struct Piece {
+        i64 tr, tc;        // first row / column in tile coordinates
+        i64 rows, cols;
+        i64 wr, wc;        // the piece's offset inside the rectangle
+    };
+    static std::vector<Piece> pieces(const Geometry& g, i64 r0, i64 c0, i64 rows, i64 cols);
+    void check_window(i64 rows, i64 cols) const;
+    void check_density(i64 block_rows, i64 block_cols) const;
+    void check_stamp(const RlePattern& p) const;
     // Collective: align the ranks right before a timed region.  Host barrier; with a device
     // transport also a 1-element all-reduce on the compute stream, waited for, so every rank leaves
     // when the collective has completed on the GPUs, not when a host barrier happened to release it.

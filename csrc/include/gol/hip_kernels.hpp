@@ -14,6 +14,7 @@
 //   init_fill/set_cells — device-side pattern init (reference: host loops over managed memory).
 //   copy_regions      — batched strided copies: 2-D halo pack/unpack and self-neighbour copies.
 //   reduce_board      — population + decomposition-invariant fingerprint.
+//   window_bytes / density / stamp — views of the live board and pattern stamping (view_kernels.hip).
 //   naive_byte_step   — byte-per-cell, thread-per-cell yardstick of the reference's algorithm class
 //                       (no printf), used only by the benchmark for comparison.
 #pragma once
@@ -153,6 +154,23 @@ void launch_copy_regions(const CopyDesc* descs, int n, i64 max_elems, hipStream_
 // out[0] += population, out[1] += fingerprint (wrapping sums); out must be zeroed by the caller.
 void launch_reduce_board(const u64* buf, const Layout& L, i64 grow0, i64 gword0, i64 gwords, u64* out,
                          hipStream_t s);
+
+// ----- views and stamping (view_kernels.hip) -----
+// A rectangle of cells in tile coordinates, inside the tile (the launchers check it).
+struct ViewRect {
+    i64 tr, tc;  // first row / column
+    i64 rows, cols;
+};
+// window_bytes: the rectangle's cells as 0/1 bytes, dst[r * cols + c] (dst 16-byte aligned).
+void launch_window_bytes(const u64* buf, const Layout& L, const ViewRect& rc, u8* dst, hipStream_t s);
+// density: counts[bi * grid_cols + bj] += live cells of the tile in block (bi, bj) of the global board, blocks of
+// block_rows rows x block_words words; (row0, gword0) is the tile's place on the board.
+void launch_density(const u64* buf, const Layout& L, i64 row0, i64 gword0, i64 block_rows, i64 block_words,
+                    i64 grid_cols, u32* counts, hipStream_t s);
+// stamp: the rectangle's cells combined with the pattern's (natural-order words in device memory, pnw per row),
+// whose cell (pr0, pc0) lands on the rectangle's first cell; mode 0 or, 1 replace, 2 xor, 3 clear.
+void launch_stamp(u64* buf, const Layout& L, const ViewRect& rc, const u64* pat, i64 pnw, i64 pr0, i64 pc0, int mode,
+                  hipStream_t s);
 
 // Yardstick: one byte per cell, one thread per cell, x-wrap + two ghost rows (reference class).
 void launch_naive_byte_step(const u8* src, u8* dst, i64 w, i64 h, const u8* above, const u8* below, int threads,

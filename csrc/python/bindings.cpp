@@ -19,6 +19,7 @@
 #include "gol/io.hpp"
 #include "gol/pattern.hpp"
 #include "gol/plan.hpp"
+#include "gol/rle.hpp"
 #include "gol/runtime.hpp"
 #include "gol/transport.hpp"
 
@@ -111,6 +112,7 @@ py::dict stats_dict(const EngineStats& s) {
     d["tile_waves"] = s.tile_waves;
     d["tuning"] = s.tuning;
     d["registered"] = s.registered;
+    d["view_bytes_d2h"] = s.view_bytes_d2h;
     return d;
 }
 
@@ -318,6 +320,42 @@ PYBIND11_MODULE(_gol, m) {
         .def("local_reduce", &Engine::local_reduce, py::call_guard<py::gil_scoped_release>())
         .def("population", &Engine::population, py::call_guard<py::gil_scoped_release>())
         .def("fingerprint", &Engine::fingerprint, py::call_guard<py::gil_scoped_release>())
+        // views and stamping (collective; global board coordinates on the torus)
+        .def(
+            "window",
+            [](Engine& e, i64 r0, i64 c0, i64 rows, i64 cols) {
+                std::vector<u8> v;
+                {
+                    py::gil_scoped_release r;
+                    v = e.window(r0, c0, rows, cols);
+                }
+                py::array_t<u8> a({(py::ssize_t)rows, (py::ssize_t)cols});
+                std::memcpy(a.mutable_data(), v.data(), v.size());
+                return a;
+            },
+            py::arg("r0"), py::arg("c0"), py::arg("rows"), py::arg("cols"))
+        .def(
+            "density",
+            [](Engine& e, i64 block_rows, i64 block_cols) {
+                std::vector<u32> v;
+                {
+                    py::gil_scoped_release r;
+                    v = e.density(block_rows, block_cols);
+                }
+                const Decomposition& d = e.geometry().dec;
+                py::array_t<u32> a({(py::ssize_t)ceil_div(d.H, block_rows), (py::ssize_t)ceil_div(d.W, block_cols)});
+                std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(u32));
+                return a;
+            },
+            py::arg("block_rows"), py::arg("block_cols"))
+        .def(
+            "stamp",
+            [](Engine& e, const RlePattern& p, i64 r0, i64 c0, const std::string& mode) {
+                const StampMode m = parse_stamp_mode(mode);
+                py::gil_scoped_release r;
+                e.stamp(p, r0, c0, m);
+            },
+            py::arg("pattern"), py::arg("r0"), py::arg("c0"), py::arg("mode") = "or")
         .def("device_barrier", &Engine::device_barrier, py::call_guard<py::gil_scoped_release>())
         .def("phase_probe", &Engine::phase_probe, py::arg("k"), py::call_guard<py::gil_scoped_release>())
         .def("time_runs", &Engine::time_runs, py::arg("gens"), py::arg("reps"), py::call_guard<py::gil_scoped_release>())
@@ -373,6 +411,42 @@ PYBIND11_MODULE(_gol, m) {
             return words_to_numpy(out, h, nw);
         },
         py::arg("words"), py::arg("w"), py::arg("gens"));
+
+    // ---- RLE patterns ---------------------------------------------------------------------
+    py::class_<RlePattern>(m, "RlePattern")
+        .def(py::init([](py::array_t<u64, py::array::c_style | py::array::forcecast> words, i64 cols, const std::string& rule) {
+                 if (words.ndim() != 2 || cols < 1 || words.shape(0) < 1 || words.shape(1) != ceil_div(cols, 64))
+                     throw py::value_error("RlePattern: words must be a (rows, ceil(cols / 64)) uint64 array");
+                 RlePattern p;
+                 p.rows = words.shape(0);
+                 p.cols = cols;
+                 p.rule = rule;
+                 p.words.assign(words.data(), words.data() + words.size());
+                 for (i64 r = 0; r < p.rows; ++r) p.words[(size_t)(r * p.nw() + p.nw() - 1)] &= word_mask(p.nw() - 1, cols);
+                 return p;
+             }),
+             py::arg("words"), py::arg("cols"), py::arg("rule") = "")
+        .def_readonly("rows", &RlePattern::rows)
+        .def_readonly("cols", &RlePattern::cols)
+        .def_readonly("rule", &RlePattern::rule)
+        .def_property_readonly("words", [](const RlePattern& p) { return words_to_numpy(p.words, p.rows, p.nw()); });
+    // (a text or a file no reader accepts is a ValueError, like a bad rule string)
+    m.def("parse_rle", [](const std::string& text) {
+        try {
+            return parse_rle(text);
+        } catch (const Error& e) {
+            throw py::value_error(e.what());
+        }
+    });
+    m.def("read_rle_file", [](const std::string& path) {
+        try {
+            return read_rle_file(path);
+        } catch (const Error& e) {
+            throw py::value_error(e.what());
+        }
+    });
+    m.def("write_rle", &write_rle);
+    m.def("write_rle_file", &write_rle_file);
 
     // ---- I/O + CLI ------------------------------------------------------------------------
     m.def("dump_filename", &io::dump_filename);

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <thread>
 
+#include "gol/bits.hpp"
 #include "gol/cpu.hpp"
 #include "gol/trace.hpp"
 
@@ -255,6 +256,129 @@ u64 Engine::population() { return t_->allreduce_sum(local_reduce().first); }
 u64 Engine::fingerprint() { return t_->allreduce_sum(local_reduce().second); }
 
 // ---------------------------------------------------------------------------------------------
+// Views and pattern stamping (collective wrappers; the backends do the rank-local part)
+// ---------------------------------------------------------------------------------------------
+
+StampMode parse_stamp_mode(const std::string& s) {
+    if (s == "or") return StampMode::Or;
+    if (s == "replace") return StampMode::Replace;
+    if (s == "xor") return StampMode::Xor;
+    if (s == "clear") return StampMode::Clear;
+    throw Error("stamp mode must be or, replace, xor or clear (got '" + s + "')");
+}
+
+std::vector<Engine::Piece> Engine::pieces(const Geometry& g, i64 r0, i64 c0, i64 rows, i64 cols) {
+    // the rectangle cut at the seams: up to two row spans x two column spans of the global board
+    struct Span {
+        i64 at, n, off;  // global start, length, offset inside the rectangle
+    };
+    auto spans = [](i64 start, i64 n, i64 size) {
+        const i64 s = pmod(start, size);
+        std::vector<Span> v;
+        const i64 first = std::min(n, size - s);
+        v.push_back({s, first, 0});
+        if (n > first) v.push_back({0, n - first, first});
+        return v;
+    };
+    std::vector<Piece> out;
+    for (const Span& rs : spans(r0, rows, g.dec.H))
+        for (const Span& cs : spans(c0, cols, g.dec.W)) {
+            const i64 ra = std::max(rs.at, g.row0), rb = std::min(rs.at + rs.n, g.row0 + g.h);
+            const i64 ca = std::max(cs.at, g.col0), cb = std::min(cs.at + cs.n, g.col0 + g.w);
+            if (ra >= rb || ca >= cb) continue;
+            out.push_back({ra - g.row0, ca - g.col0, rb - ra, cb - ca, rs.off + (ra - rs.at), cs.off + (ca - cs.at)});
+        }
+    return out;
+}
+
+void Engine::check_window(i64 rows, i64 cols) const {
+    if (rows < 1 || cols < 1 || rows > g_.dec.H || cols > g_.dec.W)
+        throw Error(strprintf("window of %lld x %lld cells: rows must be in 1..%lld and columns in 1..%lld (the board)",
+                              (long long)rows, (long long)cols, (long long)g_.dec.H, (long long)g_.dec.W));
+}
+
+void Engine::check_density(i64 block_rows, i64 block_cols) const {
+    if (block_rows < 1) throw Error(strprintf("density: block_rows must be >= 1 (got %lld)", (long long)block_rows));
+    if (block_cols < 64 || block_cols % 64 != 0)
+        throw Error(strprintf("density: block_cols must be a multiple of 64, the cells of a board word (got %lld)",
+                              (long long)block_cols));
+    if (std::min(block_rows, g_.dec.H) > (i64)0xFFFFFFFFll / std::min(block_cols, round_up(g_.dec.W, 64)))
+        throw Error("density: a block holds more than 2^32 - 1 cells, its count would not fit");
+}
+
+void Engine::check_stamp(const RlePattern& p) const {
+    if (p.rows < 1 || p.cols < 1 || (i64)p.words.size() != p.rows * p.nw())
+        throw Error(strprintf("stamp: malformed pattern (%lld x %lld cells, %zu words)", (long long)p.rows,
+                              (long long)p.cols, p.words.size()));
+    if (p.rows > g_.dec.H || p.cols > g_.dec.W)
+        throw Error(strprintf("stamp: the pattern (%lld x %lld) is larger than the board (%lld x %lld) and would overlap "
+                              "itself on the torus",
+                              (long long)p.rows, (long long)p.cols, (long long)g_.dec.H, (long long)g_.dec.W));
+    if (cfg_.compat)
+        throw Error("stamp: refused in compat mode (GOL_COMPAT=reference), whose halos are frozen at generation 0");
+}
+
+std::vector<u8> Engine::window(i64 r0, i64 c0, i64 rows, i64 cols) {
+    check_window(rows, cols);
+    std::vector<u8> out((size_t)(rows * cols), 0);
+    read_window_local(r0, c0, rows, cols, out.data(), cols);
+    if (t_->size() == 1) return out;
+    // every rank's pieces follow from the geometry: a rank sends the bytes of its pieces alone, in order
+    auto pack = [&](const std::vector<Piece>& ps, std::vector<u8>& bytes, bool unpack) {
+        size_t at = 0;
+        for (const Piece& p : ps)
+            for (i64 r = 0; r < p.rows; ++r, at += (size_t)p.cols) {
+                u8* w = &out[(size_t)((p.wr + r) * cols + p.wc)];
+                if (unpack)
+                    memcpy(w, &bytes[at], (size_t)p.cols);
+                else
+                    memcpy(&bytes[at], w, (size_t)p.cols);
+            }
+    };
+    auto bytes_of = [](const std::vector<Piece>& ps) {
+        size_t n = 0;
+        for (const Piece& p : ps) n += (size_t)(p.rows * p.cols);
+        return n;
+    };
+    const std::vector<Piece> mine = pieces(g_, r0, c0, rows, cols);
+    std::vector<u8> send(bytes_of(mine));
+    pack(mine, send, false);
+    std::vector<std::vector<u8>> all;
+    t_->gatherv(send.data(), send.size(), &all, 0);
+    if (g_.rank == 0)
+        for (int q = 1; q < t_->size(); ++q) {
+            const std::vector<Piece> ps = pieces(make_geometry(g_.dec, q), r0, c0, rows, cols);
+            if (all[(size_t)q].size() != bytes_of(ps)) throw Error(strprintf("window: rank %d sent a part of the wrong size", q));
+            pack(ps, all[(size_t)q], true);
+        }
+    t_->broadcast(out.data(), out.size(), 0);
+    return out;
+}
+
+std::vector<u32> Engine::density(i64 block_rows, i64 block_cols) {
+    check_density(block_rows, block_cols);
+    const size_t n = (size_t)(ceil_div(g_.dec.H, block_rows) * ceil_div(g_.dec.W, block_cols));
+    std::vector<u32> out(n, 0);
+    density_local(block_rows, block_cols, out.data());
+    if (t_->size() == 1) return out;
+    std::vector<std::vector<u8>> all;
+    t_->gatherv(out.data(), n * sizeof(u32), &all, 0);
+    if (g_.rank == 0)
+        for (int q = 1; q < t_->size(); ++q) {
+            if (all[(size_t)q].size() != n * sizeof(u32)) throw Error(strprintf("density: rank %d sent a grid of the wrong size", q));
+            const u32* part = reinterpret_cast<const u32*>(all[(size_t)q].data());
+            for (size_t i = 0; i < n; ++i) out[i] += part[i];
+        }
+    t_->broadcast(out.data(), n * sizeof(u32), 0);
+    return out;
+}
+
+void Engine::stamp(const RlePattern& p, i64 r0, i64 c0, StampMode mode) {
+    check_stamp(p);
+    stamp_local(p, r0, c0, mode);
+}
+
+// ---------------------------------------------------------------------------------------------
 // CPU backend
 // ---------------------------------------------------------------------------------------------
 
@@ -284,6 +408,42 @@ class CpuEngine : public Engine {
     std::pair<u64, u64> local_reduce() override {
         return {cpu::population(cur_, L_),
                 cpu::fingerprint(cur_, L_, g_.row0, g_.word0(), g_.global_words())};
+    }
+
+    void read_window_local(i64 r0, i64 c0, i64 rows, i64 cols, u8* out, i64 stride) override {
+        check_window(rows, cols);
+        for (const Piece& p : pieces(g_, r0, c0, rows, cols))
+            for (i64 r = 0; r < p.rows; ++r) {
+                const u64* row = cur_ + L_.index(p.tr + r, 0);
+                u8* o = out + (p.wr + r) * stride + p.wc;
+                for (i64 c = 0; c < p.cols; ++c) {
+                    const i64 tc = p.tc + c;
+                    o[c] = (u8)(((merge_word(row[tc >> 6]) & L_.mask(tc >> 6)) >> (tc & 63)) & 1ull);
+                }
+            }
+    }
+
+    void density_local(i64 block_rows, i64 block_cols, u32* counts) override {
+        check_density(block_rows, block_cols);
+        const i64 gcols = ceil_div(g_.dec.W, block_cols), wpb = block_cols / 64;
+        for (i64 r = 0; r < L_.h; ++r) {
+            const u64* row = cur_ + L_.index(r, 0);
+            u32* line = counts + ((g_.row0 + r) / block_rows) * gcols;
+            for (i64 c = 0; c < L_.nw; ++c)
+                line[(g_.word0() + c) / wpb] += (u32)__builtin_popcountll(row[c] & storage_mask(c, L_.w));
+        }
+    }
+
+    void stamp_local(const RlePattern& p, i64 r0, i64 c0, StampMode mode) override {
+        check_stamp(p);
+        for (const Piece& q : pieces(g_, r0, c0, p.rows, p.cols))
+            for (i64 r = 0; r < q.rows; ++r) {
+                u64* row = cur_ + L_.index(q.tr + r, 0);
+                const u64* prow = &p.words[(size_t)((q.wr + r) * p.nw())];
+                for (i64 cw = q.tc >> 6; cw <= (q.tc + q.cols - 1) >> 6; ++cw)
+                    row[cw] = stamp_word(row[cw], prow, q.wc, q.tc, q.cols, cw, (int)mode);
+            }
+        refresh_local(cur_);
     }
 
    protected:

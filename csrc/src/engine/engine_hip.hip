@@ -218,6 +218,9 @@ HipEngine::~HipEngine() {
     for (void* q : {(void*)res_status_, (void*)res_scratch_[0], (void*)res_scratch_[1]})
         if (q) hipFree(q);
     for (void* p : deferred_free_) hipFree(p);
+    for (void* p : {(void*)d_view_, (void*)d_grid_, (void*)d_pat_})
+        if (p) hipFree(p);
+    if (h_view_) hipHostFree(h_view_);
     hipFree(d_red_);
     hipHostFree(h_red_);
     hipEventDestroy(ev_ready_);

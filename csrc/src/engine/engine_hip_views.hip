@@ -1,0 +1,102 @@
+// gol-mi355x: HIP engine — windows, density maps and pattern stamping on the live board (view_kernels.hip).
+//
+// Readers first bring the canonical board up to date and drain the engine's streams, as tile_words() does;
+// the stamp then refreshes ghosts and events exactly as set_tile_words() does.  Staging buffers grow on demand
+// and are reused; an outgrown one is freed with the engine (hipFree may synchronise the whole device).
+#include "hip_engine.hpp"
+
+namespace gol {
+namespace hipeng {
+
+void HipEngine::grow_device(void** p, size_t* cap, size_t need) {
+    if (need <= *cap) return;
+    if (*p) deferred_free_.push_back(*p);
+    *p = nullptr;
+    *cap = 0;
+    HIP_CHECK(hipMalloc(p, need));
+    *cap = need;
+}
+
+u8* HipEngine::view_host(size_t need) {
+    if (need > h_view_cap_) {
+        if (h_view_) HIP_CHECK(hipHostFree(h_view_));
+        h_view_ = nullptr;
+        h_view_cap_ = 0;
+        HIP_CHECK(hipHostMalloc((void**)&h_view_, need, hipHostMallocDefault));
+        h_view_cap_ = need;
+    }
+    return h_view_;
+}
+
+void HipEngine::read_window_local(i64 r0, i64 c0, i64 rows, i64 cols, u8* out, i64 stride) {
+    check_window(rows, cols);
+    sync_canonical();
+    synchronize();
+    check_res_status();
+    const std::vector<Piece> ps = pieces(g_, r0, c0, rows, cols);
+    if (ps.empty()) return;
+    std::vector<size_t> at;  // each piece dense, at a 256-byte boundary of the staging buffers
+    size_t total = 0;
+    for (const Piece& p : ps) {
+        at.push_back(total);
+        total += (size_t)round_up(p.rows * p.cols, 256);
+    }
+    grow_device((void**)&d_view_, &d_view_cap_, total);
+    u8* host = view_host(total);
+    for (size_t i = 0; i < ps.size(); ++i) {
+        const Piece& p = ps[i];
+        const size_t n = (size_t)(p.rows * p.cols);
+        hipk::launch_window_bytes(buf_[cur_], L_, {p.tr, p.tc, p.rows, p.cols}, d_view_ + at[i], s_comp_);
+        HIP_CHECK(hipGetLastError());
+        // only the piece's bytes cross to the host
+        HIP_CHECK(hipMemcpyAsync(host + at[i], d_view_ + at[i], n, hipMemcpyDeviceToHost, s_comp_));
+        stats_.view_bytes_d2h += (u64)n;
+    }
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    for (size_t i = 0; i < ps.size(); ++i) {
+        const Piece& p = ps[i];
+        for (i64 r = 0; r < p.rows; ++r)
+            memcpy(out + (p.wr + r) * stride + p.wc, host + at[i] + (size_t)(r * p.cols), (size_t)p.cols);
+    }
+}
+
+void HipEngine::density_local(i64 block_rows, i64 block_cols, u32* counts) {
+    check_density(block_rows, block_cols);
+    sync_canonical();
+    synchronize();
+    check_res_status();
+    const i64 grows = ceil_div(g_.dec.H, block_rows), gcols = ceil_div(g_.dec.W, block_cols);
+    const size_t bytes = (size_t)(grows * gcols) * sizeof(u32);
+    grow_device((void**)&d_grid_, &d_grid_cap_, bytes);
+    u32* host = reinterpret_cast<u32*>(view_host(bytes));
+    HIP_CHECK(hipMemsetAsync(d_grid_, 0, bytes, s_comp_));
+    hipk::launch_density(buf_[cur_], L_, g_.row0, g_.word0(), block_rows, block_cols / 64, gcols, d_grid_, s_comp_);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(host, d_grid_, bytes, hipMemcpyDeviceToHost, s_comp_));  // only the grid leaves the device
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    for (i64 i = 0; i < grows * gcols; ++i) counts[i] += host[i];
+}
+
+void HipEngine::stamp_local(const RlePattern& p, i64 r0, i64 c0, StampMode mode) {
+    check_stamp(p);
+    sync_canonical();
+    synchronize();
+    check_res_status();
+    const std::vector<Piece> ps = pieces(g_, r0, c0, p.rows, p.cols);
+    if (ps.empty()) return;  // none of the pattern's cells is this rank's: its halos follow with the next exchange
+    sub_current_ = false;    // the canonical board is edited: sub-tiles reload at the next run()
+    canon_stale_ = false;
+    const size_t bytes = p.words.size() * sizeof(u64);
+    grow_device((void**)&d_pat_, &d_pat_cap_, bytes);
+    upload(d_pat_, p.words.data(), bytes);
+    for (const Piece& q : ps) {
+        hipk::launch_stamp(buf_[cur_], L_, {q.tr, q.tc, q.rows, q.cols}, d_pat_, p.nw(), q.wr, q.wc, (int)mode, s_comp_);
+        HIP_CHECK(hipGetLastError());
+    }
+    post(buf_[cur_], s_comp_);
+    mark_ready();
+    synchronize();
+}
+
+}  // namespace hipeng
+}  // namespace gol

@@ -113,6 +113,11 @@ class HipEngine : public Engine {
 
     void set_tile_words(const std::vector<u64>& dense) override;
 
+    // windows, density maps, stamping (engine_hip_views.hip)
+    void read_window_local(i64 r0, i64 c0, i64 rows, i64 cols, u8* out, i64 stride) override;
+    void density_local(i64 block_rows, i64 block_cols, u32* counts) override;
+    void stamp_local(const RlePattern& p, i64 r0, i64 c0, StampMode mode) override;
+
     std::pair<u64, u64> local_reduce() override {
         sync_canonical();
         check_res_status();
@@ -670,6 +675,15 @@ class HipEngine : public Engine {
     std::string sched_pick_;     // the schedule candidate choose_schedule picked (phase_probe times it)
     bool events_needed_ = true;  // another stream waits on ev_ready_
     std::vector<void*> deferred_free_;
+    // staging of the views (engine_hip_views.hip): window bytes, the density grid, an uploaded pattern; grown on
+    // demand (an outgrown device buffer goes to deferred_free_) and reused
+    void grow_device(void** p, size_t* cap, size_t need);
+    u8* view_host(size_t need);  // pinned
+    u8* d_view_ = nullptr;
+    u32* d_grid_ = nullptr;
+    u64* d_pat_ = nullptr;
+    u8* h_view_ = nullptr;
+    size_t d_view_cap_ = 0, d_grid_cap_ = 0, d_pat_cap_ = 0, h_view_cap_ = 0;
     std::map<i64, DevPlan> plans_;
     // GOL_SUBTILES=2 state
     bool dual_ = false;

@@ -19,6 +19,7 @@
 
 #include "gol/io.hpp"
 #include "gol/pattern.hpp"
+#include "gol/rle.hpp"
 #include "gol/trace.hpp"
 
 namespace gol {
@@ -165,7 +166,7 @@ EngineConfig engine_config(const Options& o, const std::string& backend, int dev
     c.rows_per_wave = o.rows_per_wave;
     c.waves_target = o.waves_target;
     c.kernel = env_str("GOL_KERNEL", "auto");
-    c.rule = Rule::parse(env_str("GOL_RULE", "B3/S23"));
+    c.rule = Rule::parse(o.rule.empty() ? env_str("GOL_RULE", "B3/S23") : o.rule);
     c.tile_waves = (int)env_int("GOL_TILE_WAVES", 8);
     c.tune_tile_waves = getenv("GOL_TILE_WAVES") == nullptr;
     c.transport = (o.transport == "rccl" || o.transport == "p2p") ? "device" : o.transport;
@@ -443,7 +444,41 @@ void write_metrics(const Options& o, Engine& eng, const CliArgs& a, double durat
     f << "}\n";
 }
 
-int run_rank(const CliArgs& a, const Options& o, const LaunchInfo& li, std::shared_ptr<Transport> control) {
+// GOL_PATTERN_FILE, read once before any rank starts (run_cli), and where GOL_PATTERN_AT puts it.
+struct CliPattern {
+    bool have = false, centred = true;
+    RlePattern p;
+    i64 row = 0, col = 0;
+};
+
+CliPattern load_cli_pattern(Options& o) {
+    CliPattern cp;
+    if (o.pattern_file.empty()) return cp;
+    cp.have = true;
+    cp.p = read_rle_file(o.pattern_file);
+    if (!o.pattern_at.empty()) {
+        long long r = 0, c = 0;
+        char tail = 0;
+        if (sscanf(o.pattern_at.c_str(), " %lld , %lld %c", &r, &c, &tail) != 2)
+            throw Error("GOL_PATTERN_AT must be row,col (got '" + o.pattern_at + "')");
+        cp.centred = false;
+        cp.row = r;
+        cp.col = c;
+    }
+    // the file's rule: adopted when GOL_RULE is unset, and a conflict with GOL_RULE ends the run
+    if (!cp.p.rule.empty()) {
+        const std::string env = env_str("GOL_RULE", "");
+        if (env.empty())
+            o.rule = cp.p.rule;
+        else if (Rule::parse(env) != Rule::parse(cp.p.rule))
+            throw Error("GOL_PATTERN_FILE " + o.pattern_file + " names rule " + cp.p.rule + ", GOL_RULE asks for " +
+                        Rule::parse(env).str());
+    }
+    return cp;
+}
+
+int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const LaunchInfo& li,
+             std::shared_ptr<Transport> control) {
     const int rank = control->rank(), P = control->size();
     FILE* fp = nullptr;
     if (a.on_off == 1) {
@@ -466,6 +501,12 @@ int run_rank(const CliArgs& a, const Options& o, const LaunchInfo& li, std::shar
         }
         Decomposition dec = make_decomposition((i64)a.world_size, P, o.global_mode, o.decomp, o.grid);
         Geometry g = make_geometry(dec, rank);
+        // (the same on every rank, before any engine exists)
+        constexpr i64 kRleOutMaxCells = (i64)1 << 26;
+        if (!o.rle_out.empty() && dec.H * dec.W > kRleOutMaxCells)
+            throw Error(strprintf("GOL_RLE_OUT: the %lld x %lld board has more than 2^26 cells, too large to gather on rank 0 "
+                                  "and write as RLE (a checkpoint, GOL_CHECKPOINT_EVERY, holds any board)",
+                                  (long long)dec.H, (long long)dec.W));
         PatternSpec pat = make_pattern(a.pattern, dec, o.seed);
         std::shared_ptr<Transport> t = make_data_transport(control, backend, o, device);
         EngineConfig ec = engine_config(o, backend, device);
@@ -474,6 +515,9 @@ int run_rank(const CliArgs& a, const Options& o, const LaunchInfo& li, std::shar
         std::unique_ptr<Engine> eng = Engine::create(g, ec, t);
         if (o.verbose && rank == 0) fprintf(stderr, "[gol] %s\n", eng->describe().c_str());
         eng->init(pat);
+        if (cp.have)  // (a restart, below, replaces the board, this pattern included)
+            eng->stamp(cp.p, cp.centred ? (dec.H - cp.p.rows) / 2 : cp.row, cp.centred ? (dec.W - cp.p.cols) / 2 : cp.col,
+                       StampMode::Or);
         u64 done = 0;
         if (!o.restart.empty()) done = load_checkpoint(*eng, o.restart);
         const u64 total = a.iterations;
@@ -512,6 +556,20 @@ int run_rank(const CliArgs& a, const Options& o, const LaunchInfo& li, std::shar
             fclose(fp);
             fp = nullptr;
         }
+        if (!o.rle_out.empty()) {
+            RlePattern out;
+            out.rows = dec.H;
+            out.cols = dec.W;
+            out.rule = eng->config().rule.str();
+            const std::vector<u8> cells = eng->window(0, 0, dec.H, dec.W);  // collective
+            if (rank == 0) {
+                out.words.assign((size_t)(out.rows * out.nw()), 0);
+                for (i64 r = 0; r < out.rows; ++r)
+                    for (i64 c = 0; c < out.cols; ++c)
+                        if (cells[(size_t)(r * out.cols + c)]) out.set(r, c);
+                write_rle_file(o.rle_out, out);
+            }
+        }
         t->barrier();
         return 0;
     } catch (const ContractError& e) {
@@ -537,6 +595,8 @@ int run_cli(int argc, char** argv) {
         // GOL_RULE (read again per rank in engine_config, beside GOL_KERNEL): a bad value ends the job here,
         // with the parse error, before any rank starts
         (void)Rule::parse(env_str("GOL_RULE", "B3/S23"));  // (GOL_VERBOSE=1: describe() names the rule)
+        // GOL_PATTERN_FILE likewise: an unreadable file, or one whose rule GOL_RULE contradicts, ends the job here
+        const CliPattern cp = load_cli_pattern(o);
         LaunchInfo li = detect_launch(o);
         if (li.mode == "threads") {
             auto group = make_thread_group(li.size);
@@ -546,7 +606,7 @@ int run_cli(int argc, char** argv) {
                 th.emplace_back([&, r] {
                     try {
                         auto t = std::make_shared<ThreadTransport>(group, r);
-                        status[(size_t)r] = run_rank(a, o, li, t);
+                        status[(size_t)r] = run_rank(a, o, cp, li, t);
                     } catch (const std::exception& e) {
                         fprintf(stderr, "[gol] rank %d: %s\n", r, e.what());
                         fflush(stderr);
@@ -563,7 +623,7 @@ int run_cli(int argc, char** argv) {
         auto control = make_control_transport(li, &argc, &argv);
         int st = 0;
         try {
-            st = run_rank(a, o, li, control);
+            st = run_rank(a, o, cp, li, control);
         } catch (const std::exception& e) {
             fprintf(stderr, "[gol] rank %d: %s\n", control->rank(), e.what());
             fflush(stderr);

@@ -193,6 +193,93 @@ class Simulation:
     def describe(self) -> str:
         return self.engine.describe()
 
+    # -- views and patterns ----------------------------------------------------------------
+    # Global board coordinates on the torus; all of these are collective, and every rank gets the same result.
+    def window(self, r0: int, c0: int, rows: int, cols: int) -> np.ndarray:
+        """``rows x cols`` cells of the global board from ``(r0, c0)`` on as a uint8 array.  The window may
+        start anywhere (coordinates wrap), cross the board's seams and any rank boundary; it is at most the
+        board's size.  On the HIP backend only the window's bytes leave the device."""
+        return self.engine.window(int(r0), int(c0), int(rows), int(cols))
+
+    def density(self, block_rows: int, block_cols: Optional[int] = None) -> np.ndarray:
+        """Live cells per ``block_rows x block_cols`` block of the global board: a uint32 array of
+        ``ceil(H / block_rows) x ceil(W / block_cols)`` counts (edge blocks are partial).  ``block_cols``
+        (default: ``block_rows``) must be a multiple of 64."""
+        block_cols = block_rows if block_cols is None else block_cols
+        if int(block_rows) < 1 or int(block_cols) < 64 or int(block_cols) % 64:
+            raise ValueError(f"density blocks are >= 1 rows x a multiple of 64 columns, got {block_rows} x {block_cols}")
+        return self.engine.density(int(block_rows), int(block_cols))
+
+    @staticmethod
+    def _pattern(pattern):
+        """An RLE path, RLE text, a 2-D 0/1 array or a native RlePattern -> native RlePattern."""
+        from ..ops.rle import pattern_from_cells
+
+        if isinstance(pattern, _gol.RlePattern):
+            return pattern
+        if isinstance(pattern, os.PathLike):
+            pattern = os.fspath(pattern)
+        if isinstance(pattern, str):
+            if "!" in pattern or "\n" in pattern:  # (no path holds RLE's end mark or a line break)
+                return _gol.parse_rle(pattern)
+            if not os.path.exists(pattern):
+                raise FileNotFoundError(f"no RLE file {pattern!r}")
+            return _gol.read_rle_file(pattern)
+        return pattern_from_cells(pattern)
+
+    def stamp(self, pattern, at="center", mode: str = "or") -> "Simulation":
+        """Combine a pattern (an RLE path, RLE text or a 2-D 0/1 array) with the live board, its first cell at
+        ``at = (row, col)`` or centred.  ``mode``: ``"or"``, ``"replace"`` (the pattern's bounding rectangle is
+        overwritten), ``"xor"`` or ``"clear"`` (cells die where the pattern is live).  The pattern may cross
+        the seams and rank boundaries; one larger than the board is refused, and so is ``compat`` mode."""
+        p = self._pattern(pattern)
+        if mode not in ("or", "replace", "xor", "clear"):
+            raise ValueError(f"stamp mode must be or, replace, xor or clear, got {mode!r}")
+        H, W = self.decomposition.H, self.decomposition.W
+        if p.rows > H or p.cols > W:
+            raise ValueError(f"the pattern ({p.rows} x {p.cols}) is larger than the board ({H} x {W})")
+        if self.config.compat:
+            raise ValueError("stamp is refused in compat mode: its halos are frozen at generation 0")
+        if isinstance(at, str):
+            if at != "center":
+                raise ValueError(f"at must be (row, col) or 'center', got {at!r}")
+            at = ((H - p.rows) // 2, (W - p.cols) // 2)
+        self.engine.stamp(p, int(at[0]), int(at[1]), mode)
+        return self
+
+    def load_rle(self, path, at="center") -> "Simulation":
+        """An empty board (generation 0) with the file's pattern on it.  Raises if the file names a rule
+        other than the simulation's."""
+        p = self._pattern(path)
+        if p.rule and p.rule != self.config.rule:
+            raise ValueError(f"the RLE pattern names rule {p.rule}, this simulation runs {self.config.rule}")
+        self.init(0)
+        return self.stamp(p, at=at, mode="or")
+
+    def save_rle(self, path, window=None) -> None:
+        """Write ``window = (r0, c0, rows, cols)`` (default: the whole board) as an RLE file with the
+        simulation's rule.  Collective; rank 0 writes."""
+        from ..ops.rle import pattern_from_cells
+
+        r0, c0, rows, cols = window if window is not None else (0, 0, self.decomposition.H, self.decomposition.W)
+        cells = self.window(r0, c0, rows, cols)
+        if self.geometry.rank == 0:
+            _gol.write_rle_file(os.fspath(path), pattern_from_cells(cells, self.config.rule))
+
+    @classmethod
+    def from_rle(cls, path, N: int, *, at="center", **kw) -> "Simulation":
+        """A simulation of side ``N`` under the file's rule (the default rule when it names none) with the
+        file's pattern on an otherwise empty board."""
+        p = cls._pattern(path)
+        if p.rule:
+            if "rule" in kw:
+                c = _gol.EngineConfig()
+                c.rule = kw["rule"]
+                if c.rule != p.rule:
+                    raise ValueError(f"RLE file {path!r} names rule {p.rule}, the call asks for {c.rule}")
+            kw["rule"] = p.rule
+        return cls(N, **kw).load_rle(p, at=at)
+
     # -- I/O -------------------------------------------------------------------------------
     def dump(self, path: Optional[str] = None) -> str:
         """Write this rank's reference-format dump file (collective); returns the path."""

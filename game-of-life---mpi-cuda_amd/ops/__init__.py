@@ -12,6 +12,7 @@ from .oracle import (  # noqa: F401
     torch_step,
     torch_step_rule,
 )
+from .rle import parse_rle, pattern_cells, pattern_from_cells, write_rle  # noqa: F401
 from .._native import _gol as _native
 
 
