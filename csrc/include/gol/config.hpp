@@ -55,6 +55,8 @@ struct Options {
     std::string pattern_at = "";    // GOL_PATTERN_AT  row,col of the file's first cell (default: centred)
     std::string rle_out = "";       // GOL_RLE_OUT   rank 0 writes the final global board as RLE (<= 2^26 cells)
     std::string rule = "";          // the run's rule when GOL_PATTERN_FILE names one and GOL_RULE is unset
+    std::string boundary = "";      // the run's boundary when GOL_PATTERN_FILE names a topology and GOL_BOUNDARY is
+                                    // unset (GOL_BOUNDARY torus | dead is read beside GOL_RULE, runtime.cpp)
 };
 
 Options options_from_env();

@@ -14,13 +14,36 @@
 namespace gol {
 namespace cpu {
 
+// The board's boundary and the tile's place on the global board (what a bounded step needs to know which of
+// the cells it sees lie outside the board).  The default is the torus, where the place is not used.
+struct Edges {
+    Boundary boundary = Boundary::Torus;
+    i64 row0 = 0;   // global row of tile row 0
+    i64 rows = 0;   // rows of the global board (H)
+    i64 word0 = 0;  // global word index of tile word 0
+    i64 cols = 0;   // columns of the global board (W)
+
+    Edges() = default;
+    Edges(Boundary b, const Geometry& g) : boundary(b), row0(g.row0), rows(g.dec.H), word0(g.word0()), cols(g.dec.W) {}
+    bool dead() const { return boundary == Boundary::Dead; }
+};
+
+// Boundary::Dead: clear every cell of rows [r_lo, r_hi) (words -1 .. nw) that lies outside the global board:
+// whole rows whose global row is outside [0, H), words whose global index is outside [0, ceil(W / 64)), and the
+// bits past column W of the board's last word.  (No-op on the torus.)
+void mask_rows(u64* buf, const Layout& L, i64 r_lo, i64 r_hi, const Edges& edges);
+
 // One generation for rows [r_lo, r_hi) (all words -1 .. nw) of `dst` from `src`.  B3/S23 runs the
 // specialised gates (bits.hpp rule64); any other rule a generic bit-sliced path (4-plane count, then
-// next = x ? S[count] : B[count] from the rule's masks), chosen once per call.
-void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, const Rule& rule = Rule());
+// next = x ? S[count] : B[count] from the rule's masks), chosen once per call.  On a bounded board the
+// output rows are masked (mask_rows); the caller masks the input.
+void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, const Rule& rule = Rule(),
+               const Edges& edges = Edges());
 
-// k generations (k <= L.R).  Ping-pongs between a and b; returns the buffer with the result.
-u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule = Rule());
+// k generations (k <= L.R).  Ping-pongs between a and b; returns the buffer with the result.  On a bounded
+// board the input rows [-k, h + k) of `a` are masked in place first (the ghost rows and words hold what the
+// torus machinery delivered across the board's edges), then every generation's output.
+u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule = Rule(), const Edges& edges = Edges());
 
 // x-periodic ghost words (and tail ghost bits) for rows [r_lo, r_hi).
 void fill_ghost_cols_wrap(u64* buf, const Layout& L, i64 r_lo, i64 r_hi);

@@ -54,6 +54,10 @@ struct EngineConfig {
                                       // rule (the generic life-like-rule kernel, also for B3/S23)
     Rule rule;                        // the life-like rule (default B3/S23; GOL_RULE).  Any other rule runs
                                       // the generic paths: cpu::step_rows' bit-sliced count, step_rule on HIP
+    Boundary boundary = Boundary::Torus;  // Torus (the reference) | Dead: cells outside the global board are
+                                      // dead in every generation (GOL_BOUNDARY).  The torus machinery (ghost
+                                      // fills, exchanges with the wrap-around neighbour) keeps running; what it
+                                      // delivers across a global edge is masked away.  HIP: step_rule_bounded
     int tile_waves = 8;               // tile kernel: waves per workgroup (4, 8, 16)
     bool tune_tile_waves = true;      // GOL_KERNEL=auto may also try 8 waves (false: GOL_TILE_WAVES set)
     std::string transport = "auto";   // auto | device | host  (host = stage halos through host memory)
@@ -101,6 +105,7 @@ struct EngineStats {
     double t_compute_ms = 0;   // profile only
     std::string kernel;        // stencil kernel in use (HIP: temporal | tile | lds | rule@K; CPU: cpu)
     std::string rule;          // the rule, canonical (B3/S23)
+    std::string boundary;      // torus | dead
     std::string schedule;      // superstep schedule: local (no neighbours) | split | full
     std::string tuning;        // init-time measurements behind the auto choices (HIP)
     bool registered = false;   // HIP + RCCL: the boards are registered with the communicator (zero-copy halos)
@@ -135,6 +140,7 @@ class Engine {
     // ----- views and pattern stamping -----
     // Global board coordinates on the torus: a window or a pattern may start anywhere (r0, c0 are taken
     // modulo the board), cross the board's seams and any rank boundary; it is at most the board's size.
+    // On a bounded board the rectangle must lie inside the board (0 <= r0, r0 + rows <= H, likewise columns).
     // The *_local virtuals do this rank's part, the wrappers below them are collective and return the
     // whole result on every rank (the parts travel over the control plane: gatherv to rank 0, broadcast).
     // Arguments are validated before any communication: a bad call throws on every rank, none hangs.
@@ -159,9 +165,12 @@ class Engine {
         i64 wr, wc;        // the piece's offset inside the rectangle
     };
     static std::vector<Piece> pieces(const Geometry& g, i64 r0, i64 c0, i64 rows, i64 cols);
+    // (on a bounded board the rectangle must lie inside the board: the overloads with r0, c0)
     void check_window(i64 rows, i64 cols) const;
+    void check_window(i64 r0, i64 c0, i64 rows, i64 cols) const;
     void check_density(i64 block_rows, i64 block_cols) const;
     void check_stamp(const RlePattern& p) const;
+    void check_stamp(const RlePattern& p, i64 r0, i64 c0) const;
     // Collective: align the ranks right before a timed region.  Host barrier; with a device
     // transport also a 1-element all-reduce on the compute stream, waited for, so every rank leaves
     // when the collective has completed on the GPUs, not when a host barrier happened to release it.
@@ -213,7 +222,9 @@ class Engine {
         return g_.nbr[DIR_W] == g_.rank && g_.nbr[DIR_E] == g_.rank && !(xchg_self_ && two_d());
     }
     bool self_y() const { return g_.nbr[DIR_N] == g_.rank && g_.nbr[DIR_S] == g_.rank && !xchg_self_; }
-    bool xwrap_by_plan() const { return self_x() && L_.aligned(); }
+    // (not on a bounded board: a halo lane that streamed word nw - 1 could not tell that it is outside the board)
+    bool xwrap_by_plan() const { return self_x() && L_.aligned() && !dead_edges(); }
+    bool dead_edges() const { return cfg_.boundary == Boundary::Dead; }
     // Rows of the smallest tile of the job (identical on every rank).
     i64 min_tile_rows() const {
         i64 m = g_.dec.H;

@@ -38,6 +38,12 @@ inline int dir_dx(Dir d) {
 }
 const char* dir_name(Dir d);
 
+// What lies beyond the edges of the global board: its own opposite edge (the reference's torus), or dead
+// cells in every generation (a bounded board: a plane cut to H x W).
+enum class Boundary : int { Torus = 0, Dead = 1 };
+Boundary parse_boundary(const std::string& s);  // torus | dead; anything else throws, naming it
+const char* boundary_name(Boundary b);
+
 // How the global board is laid out across ranks.
 struct Decomposition {
     i64 H = 0, W = 0;       // global rows / columns

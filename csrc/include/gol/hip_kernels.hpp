@@ -7,6 +7,8 @@
 //                       load addressing.  Replaces gol_kernel + the per-generation sync/swap.
 //   step_rule<K>      — step_temporal's streaming wave with a generic finish: any B0-free life-like rule
 //                       B.../S... from two run-time masks (rule_kernel.hip; K = 1..8).
+//   step_rule_bounded<K> — step_rule on a bounded board (dead cells beyond the global edges): the loaded row and
+//                       every level masked to the board's cells (rule_bounded_kernel.hip; K = 1..8).
 //   step_lds          — single-generation LDS-tiled variant (tile + ghost words staged in LDS);
 //                       kept as a measured alternative (GOL_KERNEL=lds).
 //   fill_ghost_cols   — x-periodic ghost words for widths that are not a multiple of 64.
@@ -82,6 +84,18 @@ int max_rule_depth();
 int rule_blocks_per_cu(int k, u32 flags);
 void launch_step_rule(int k, const Rule& rule, const u64* src, u64* dst, const LaneDesc* plan, i64 n_waves,
                       const StepParams& p, hipStream_t s);
+// step_rule_bounded<K> (rule_bounded_kernel.hip): step_rule on a bounded board (Boundary::Dead).  Cells outside
+// the global board are dead at the input and at every level of the pass.  Same plans (built without x-wrap, so
+// a halo lane's column tells that it is outside), same StepParams, same rows and words read and written.
+struct BoardEdges {
+    i64 row0 = 0;   // global row of tile row 0
+    i64 rows = 0;   // rows of the global board
+    i64 word0 = 0;  // global word index of tile word 0
+    i64 cols = 0;   // columns of the global board
+};
+int rule_bounded_blocks_per_cu(int k, u32 flags);
+void launch_step_rule_bounded(int k, const Rule& rule, const BoardEdges& edges, const u64* src, u64* dst,
+                              const LaneDesc* plan, i64 n_waves, const StepParams& p, hipStream_t s);
 // LDS-resident temporal kernel (step_tile): one workgroup of `nw_per_wg` (4, 8, 16) waves per plan
 // wave; `rows` = the plan's rows per chunk (<= tile_max_rows(k), the 160 KiB LDS limit).
 constexpr size_t kMaxLdsBytes = 160 * 1024;

@@ -107,6 +107,7 @@ py::dict stats_dict(const EngineStats& s) {
     d["t_compute_ms"] = s.t_compute_ms;
     d["kernel"] = s.kernel;
     d["rule"] = s.rule;
+    d["boundary"] = s.boundary;
     d["schedule"] = s.schedule;
     d["kernel_depth"] = s.kernel_depth;
     d["tile_waves"] = s.tile_waves;
@@ -279,6 +280,16 @@ PYBIND11_MODULE(_gol, m) {
                 } catch (const Error& e) {
                     throw py::value_error(e.what());
                 }
+            })
+        // the board's boundary: "torus" (default) or "dead" (a bounded board); any other value is a ValueError
+        .def_property(
+            "boundary", [](const EngineConfig& c) { return std::string(boundary_name(c.boundary)); },
+            [](EngineConfig& c, const std::string& s) {
+                try {
+                    c.boundary = parse_boundary(s);
+                } catch (const Error& e) {
+                    throw py::value_error(e.what());
+                }
             });
     // rule string -> (birth, survive): bit c of birth / survive = a dead / live cell with c live neighbours lives
     m.def("parse_rule", [](const std::string& s) {
@@ -414,18 +425,29 @@ PYBIND11_MODULE(_gol, m) {
 
     // ---- RLE patterns ---------------------------------------------------------------------
     py::class_<RlePattern>(m, "RlePattern")
-        .def(py::init([](py::array_t<u64, py::array::c_style | py::array::forcecast> words, i64 cols, const std::string& rule) {
+        .def(py::init([](py::array_t<u64, py::array::c_style | py::array::forcecast> words, i64 cols, const std::string& rule,
+                         const std::string& topology, i64 bound_cols, i64 bound_rows) {
                  if (words.ndim() != 2 || cols < 1 || words.shape(0) < 1 || words.shape(1) != ceil_div(cols, 64))
                      throw py::value_error("RlePattern: words must be a (rows, ceil(cols / 64)) uint64 array");
+                 if (topology.empty() ? (bound_cols != 0 || bound_rows != 0)
+                                      : ((topology != "T" && topology != "P") || bound_cols < 1 || bound_rows < 1))
+                     throw py::value_error("RlePattern: topology is '', 'T' or 'P', with a board of >= 1 x 1 cells when set");
                  RlePattern p;
                  p.rows = words.shape(0);
                  p.cols = cols;
                  p.rule = rule;
+                 p.topology = topology;
+                 p.bound_cols = bound_cols;
+                 p.bound_rows = bound_rows;
                  p.words.assign(words.data(), words.data() + words.size());
                  for (i64 r = 0; r < p.rows; ++r) p.words[(size_t)(r * p.nw() + p.nw() - 1)] &= word_mask(p.nw() - 1, cols);
                  return p;
              }),
-             py::arg("words"), py::arg("cols"), py::arg("rule") = "")
+             py::arg("words"), py::arg("cols"), py::arg("rule") = "", py::arg("topology") = "", py::arg("bound_cols") = 0,
+             py::arg("bound_rows") = 0)
+        .def_readonly("topology", &RlePattern::topology)
+        .def_readonly("bound_cols", &RlePattern::bound_cols)
+        .def_readonly("bound_rows", &RlePattern::bound_rows)
         .def_readonly("rows", &RlePattern::rows)
         .def_readonly("cols", &RlePattern::cols)
         .def_readonly("rule", &RlePattern::rule)

@@ -11,6 +11,14 @@ const char* dir_name(Dir d) {
     return n[d];
 }
 
+Boundary parse_boundary(const std::string& s) {
+    if (s == "torus") return Boundary::Torus;
+    if (s == "dead") return Boundary::Dead;
+    throw Error("boundary must be torus or dead (got '" + s + "')");
+}
+
+const char* boundary_name(Boundary b) { return b == Boundary::Dead ? "dead" : "torus"; }
+
 static std::vector<i64> even_split(i64 total, int parts, i64 unit) {
     // Split `total` into `parts` contiguous pieces in units of `unit` (the last piece absorbs the
     // remainder that is not a whole unit).  Starts are multiples of `unit`.

@@ -66,7 +66,32 @@ void step_rows_generic(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 
 
 }  // namespace
 
-void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, const Rule& rule) {
+void mask_rows(u64* buf, const Layout& L, i64 r_lo, i64 r_hi, const Edges& edges) {
+    if (!edges.dead()) return;
+    const i64 n = L.nw + 2, gwords = ceil_div(edges.cols, 64);
+    const u64 tail = storage_mask(gwords - 1, edges.cols);
+    for (i64 r = r_lo; r < r_hi; ++r) {
+        u64* row = buf + L.index(r, -1);
+        const i64 gr = edges.row0 + r;
+        if (gr < 0 || gr >= edges.rows) {
+            std::memset(row, 0, (size_t)n * 8);
+            continue;
+        }
+        for (i64 j = 0; j < n; ++j) {
+            const i64 gw = edges.word0 + j - 1;
+            if (gw < 0 || gw >= gwords)
+                row[j] = 0;
+            else if (gw == gwords - 1)
+                row[j] &= tail;
+        }
+    }
+}
+
+void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, const Rule& rule, const Edges& edges) {
+    if (edges.dead()) {  // the torus step, then the cells outside the board cleared
+        step_rows(src, dst, L, r_lo, r_hi, rule, Edges());
+        return mask_rows(dst, L, r_lo, r_hi, edges);
+    }
     if (!rule.is_conway()) return step_rows_generic(src, dst, L, r_lo, r_hi, rule);  // (one branch per call)
     const i64 n = L.nw + 2;  // words -1 .. nw
 #pragma omp parallel for schedule(static) if ((r_hi - r_lo) * n > 16384)
@@ -88,13 +113,14 @@ void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, co
     }
 }
 
-u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule) {
+u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges) {
     if (k < 1 || k > L.R) throw Error(strprintf("superstep depth %d outside 1..%d", k, L.R));
     u64* src = a;
     u64* dst = b;
+    mask_rows(src, L, -(i64)k, L.h + k, edges);
     for (int g = 0; g < k; ++g) {
         i64 ext = k - 1 - g;
-        step_rows(src, dst, L, -ext, L.h + ext, rule);
+        step_rows(src, dst, L, -ext, L.h + ext, rule, edges);
         std::swap(src, dst);
     }
     return src;

@@ -33,6 +33,16 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
                     throw Error("kernel '" + cfg_.kernel + "' implements B3/S23 only, not rule " + rs +
                                 " (use kernel auto or rule)");
     }
+    if (cfg_.boundary != Boundary::Torus && cfg_.boundary != Boundary::Dead)
+        throw Error(strprintf("boundary must be torus or dead (got the value %d)", (int)cfg_.boundary));
+    if (dead_edges()) {
+        if (cfg_.compat) throw Error("GOL_COMPAT=reference with boundary dead: the reference is a torus");
+        if (cfg_.subtiles == 2) throw Error("two sub-tiles per rank (GOL_SUBTILES=2) implement the torus only, not boundary dead");
+        if (cfg_.backend == "hip")
+            for (const char* k : {"temporal", "tile", "pipe", "resident", "lds"})
+                if (cfg_.kernel == k)
+                    throw Error("kernel '" + cfg_.kernel + "' implements the torus only, not boundary dead (use kernel auto or rule)");
+    }
     if (t_->size() != g_.dec.P || t_->rank() != g_.rank)
         throw Error(strprintf("transport (rank %d of %d) does not match the geometry (rank %d of %d)", t_->rank(),
                               t_->size(), g_.rank, g_.dec.P));
@@ -60,7 +70,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     const bool sub_tall = cfg_.backend == "hip" && (cfg_.subtiles == 2 || cfg_.subtiles < 0) && !two_d() && strip_rows >= kSubtileMinRows &&
                           g_.dec.W % 64 == 0 && !cfg_.force_split && !cfg_.profile && !cfg_.compat &&
                           cfg_.kernel != "lds" && cfg_.kernel != "tile" && cfg_.kernel != "pipe" &&
-                          cfg_.kernel != "rule" && cfg_.rule.is_conway();
+                          cfg_.kernel != "rule" && cfg_.rule.is_conway() && !dead_edges();
     // (1-D strips with neighbours: 128 measured 1-3% faster than 64 through RCCL self-exchange,
     // 4096 x 32768 2.44 -> 2.36, 8192 x 65536 5.93 -> 5.85 us/gen; profiles/per_rank_tiles_self_exchange.txt)
     const int want = cfg_.halo_depth > 0 ? cfg_.halo_depth : (sub_tall || tall_strips ? 128 : (tall_tiles ? 56 : 32));
@@ -73,6 +83,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     L_ = Layout(g_.h, g_.w, R);
     stats_.depth = R;
     stats_.rule = cfg_.rule.str();
+    stats_.boundary = boundary_name(cfg_.boundary);
     std::string f = env_str("GOL_FAULT", "");
     if (!f.empty()) {
         int fr = -1;
@@ -125,10 +136,11 @@ std::unique_ptr<Engine> Engine::create(const Geometry& g, const EngineConfig& c,
 
 std::string Engine::describe() const {
     const std::string wg = cfg_.backend == "hip" ? strprintf(", tile workgroup %d waves", cfg_.tile_waves) : "";
-    return strprintf("%s backend, %s, rank %d tile %lldx%lld at (%lld,%lld), halo depth %d, transport %s%s%s, rule %s",
+    return strprintf("%s backend, %s, rank %d tile %lldx%lld at (%lld,%lld), halo depth %d, transport %s%s%s, rule %s%s",
                      backend_name().c_str(), g_.dec.describe().c_str(), g_.rank, (long long)g_.h, (long long)g_.w,
                      (long long)g_.row0, (long long)g_.col0, L_.R, t_->name().c_str(), wg.c_str(),
-                     cfg_.compat ? ", compat=reference" : "", cfg_.rule.str().c_str());
+                     cfg_.compat ? ", compat=reference" : "", cfg_.rule.str().c_str(),
+                     dead_edges() ? ", boundary dead" : "");
 }
 
 std::vector<Engine::HaloItem> Engine::halo_items(int k) const {
@@ -171,14 +183,22 @@ void Engine::init(const PatternSpec& p) {
     stats_.schedule = halo_items(L_.R).empty() ? "local" : "full";
     stats_.kernel_depth = L_.R;
     stats_.rule = cfg_.rule.str();
+    stats_.boundary = boundary_name(cfg_.boundary);
     if (t_->size() > 1) {
-        // every rank must run the same rule: agreed like the schedule, by reductions every rank sees
-        // (so on a mismatch every rank raises and none waits for a peer)
-        const double code = (double)cfg_.rule.code();
+        // every rank must run the same rule on the same boundary: agreed like the schedule, by reductions every
+        // rank sees (so on a mismatch every rank raises and none waits for a peer).  One code: the rule's 32 bits,
+        // the boundary above them (exact in a double).
+        const double code = (double)cfg_.rule.code() + (double)((u64)cfg_.boundary << 32);
         const double lo = t_->allreduce_min(code), hi = t_->allreduce_max(code);
-        if (lo != hi)
+        if (lo != hi) {
+            const u64 ulo = (u64)lo, uhi = (u64)hi;
+            if ((ulo >> 32) != (uhi >> 32))
+                throw Error(strprintf("the ranks disagree on the boundary: rank %d has %s (%s .. %s over the ranks)", g_.rank,
+                                      stats_.boundary.c_str(), boundary_name((Boundary)(ulo >> 32)),
+                                      boundary_name((Boundary)(uhi >> 32))));
             throw Error(strprintf("the ranks disagree on the rule: rank %d has %s (rule codes 0x%x .. 0x%x over the ranks)",
-                                  g_.rank, stats_.rule.c_str(), (unsigned)lo, (unsigned)hi));
+                                  g_.rank, stats_.rule.c_str(), (unsigned)(ulo & 0xFFFFFFFFu), (unsigned)(uhi & 0xFFFFFFFFu)));
+        }
     }
     do_init(p);
     if (cfg_.compat) setup_compat();
@@ -297,6 +317,15 @@ void Engine::check_window(i64 rows, i64 cols) const {
                               (long long)rows, (long long)cols, (long long)g_.dec.H, (long long)g_.dec.W));
 }
 
+void Engine::check_window(i64 r0, i64 c0, i64 rows, i64 cols) const {
+    check_window(rows, cols);
+    if (dead_edges() && (r0 < 0 || c0 < 0 || r0 + rows > g_.dec.H || c0 + cols > g_.dec.W))
+        throw Error(strprintf("window of %lld x %lld cells at (%lld, %lld) does not lie inside the bounded %lld x %lld board "
+                              "(boundary dead: nothing wraps)",
+                              (long long)rows, (long long)cols, (long long)r0, (long long)c0, (long long)g_.dec.H,
+                              (long long)g_.dec.W));
+}
+
 void Engine::check_density(i64 block_rows, i64 block_cols) const {
     if (block_rows < 1) throw Error(strprintf("density: block_rows must be >= 1 (got %lld)", (long long)block_rows));
     if (block_cols < 64 || block_cols % 64 != 0)
@@ -304,6 +333,15 @@ void Engine::check_density(i64 block_rows, i64 block_cols) const {
                               (long long)block_cols));
     if (std::min(block_rows, g_.dec.H) > (i64)0xFFFFFFFFll / std::min(block_cols, round_up(g_.dec.W, 64)))
         throw Error("density: a block holds more than 2^32 - 1 cells, its count would not fit");
+}
+
+void Engine::check_stamp(const RlePattern& p, i64 r0, i64 c0) const {
+    check_stamp(p);
+    if (dead_edges() && (r0 < 0 || c0 < 0 || r0 + p.rows > g_.dec.H || c0 + p.cols > g_.dec.W))
+        throw Error(strprintf("stamp: the pattern (%lld x %lld) at (%lld, %lld) does not lie inside the bounded %lld x %lld "
+                              "board (boundary dead: nothing wraps)",
+                              (long long)p.rows, (long long)p.cols, (long long)r0, (long long)c0, (long long)g_.dec.H,
+                              (long long)g_.dec.W));
 }
 
 void Engine::check_stamp(const RlePattern& p) const {
@@ -319,7 +357,7 @@ void Engine::check_stamp(const RlePattern& p) const {
 }
 
 std::vector<u8> Engine::window(i64 r0, i64 c0, i64 rows, i64 cols) {
-    check_window(rows, cols);
+    check_window(r0, c0, rows, cols);
     std::vector<u8> out((size_t)(rows * cols), 0);
     read_window_local(r0, c0, rows, cols, out.data(), cols);
     if (t_->size() == 1) return out;
@@ -374,7 +412,7 @@ std::vector<u32> Engine::density(i64 block_rows, i64 block_cols) {
 }
 
 void Engine::stamp(const RlePattern& p, i64 r0, i64 c0, StampMode mode) {
-    check_stamp(p);
+    check_stamp(p, r0, c0);
     stamp_local(p, r0, c0, mode);
 }
 
@@ -411,7 +449,7 @@ class CpuEngine : public Engine {
     }
 
     void read_window_local(i64 r0, i64 c0, i64 rows, i64 cols, u8* out, i64 stride) override {
-        check_window(rows, cols);
+        check_window(r0, c0, rows, cols);
         for (const Piece& p : pieces(g_, r0, c0, rows, cols))
             for (i64 r = 0; r < p.rows; ++r) {
                 const u64* row = cur_ + L_.index(p.tr + r, 0);
@@ -435,7 +473,7 @@ class CpuEngine : public Engine {
     }
 
     void stamp_local(const RlePattern& p, i64 r0, i64 c0, StampMode mode) override {
-        check_stamp(p);
+        check_stamp(p, r0, c0);
         for (const Piece& q : pieces(g_, r0, c0, p.rows, p.cols))
             for (i64 r = 0; r < q.rows; ++r) {
                 u64* row = cur_ + L_.index(q.tr + r, 0);
@@ -496,7 +534,7 @@ class CpuEngine : public Engine {
             exchange(k);
             if (self_y()) cpu::fill_ghost_rows_wrap(cur_, L_);
         }
-        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule);
+        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, cpu::Edges(cfg_.boundary, g_));
         if (res != cur_) std::swap(cur_, oth_);
         if (self_x()) cpu::fill_ghost_cols_wrap(cur_, L_, 0, L_.h);
     }

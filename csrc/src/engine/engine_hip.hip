@@ -40,7 +40,8 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
     kernel_ = cfg_.kernel;
     // A non-Conway rule, or kernel "rule" (B3/S23 through the generic kernel: its cross-check), runs step_rule
     // in every pass of every plan kind.  (Engine::Engine refused the specialised kernels with such a rule.)
-    rule_ = kernel_ == "rule" || !cfg_.rule.is_conway();
+    // A bounded board runs step_rule_bounded, for every rule including B3/S23 (there is no bounded step_temporal).
+    rule_ = kernel_ == "rule" || !cfg_.rule.is_conway() || dead_edges();
     if (rule_ && kernel_ == "auto") kernel_ = "rule";  // (any other name is refused below)
     hipk::ensure_trash();  // before any launch or graph capture
     // Kernel pass depth K (generations per HBM pass) vs halo depth R (generations per
@@ -615,7 +616,11 @@ void HipEngine::launch(int kind, int k, i64 e, const u64* src, u64* dst, hipStre
             hipk::launch_step_pipe(g->nw, g->l, src, dst, p.d, p.waves, sp, s);
             pipe_used_ = true;
         } else if (pk == PK_RULE) {
-            hipk::launch_step_rule(k, cfg_.rule, src, dst, p.d, p.waves, sp, s);
+            if (dead_edges())
+                hipk::launch_step_rule_bounded(k, cfg_.rule, {g_.row0, g_.dec.H, g_.word0(), g_.dec.W}, src, dst, p.d,
+                                               p.waves, sp, s);
+            else
+                hipk::launch_step_rule(k, cfg_.rule, src, dst, p.d, p.waves, sp, s);
         } else
             hipk::launch_step(k, src, dst, p.d, p.waves, sp, s);
     }

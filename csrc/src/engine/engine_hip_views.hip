@@ -29,7 +29,7 @@ u8* HipEngine::view_host(size_t need) {
 }
 
 void HipEngine::read_window_local(i64 r0, i64 c0, i64 rows, i64 cols, u8* out, i64 stride) {
-    check_window(rows, cols);
+    check_window(r0, c0, rows, cols);
     sync_canonical();
     synchronize();
     check_res_status();
@@ -78,7 +78,7 @@ void HipEngine::density_local(i64 block_rows, i64 block_cols, u32* counts) {
 }
 
 void HipEngine::stamp_local(const RlePattern& p, i64 r0, i64 c0, StampMode mode) {
-    check_stamp(p);
+    check_stamp(p, r0, c0);
     sync_canonical();
     synchronize();
     check_res_status();

@@ -304,6 +304,7 @@ class HipEngine : public Engine {
     bool depth_ok(int k) const { return rule_ ? hipk::rule_depth_supported(k) : hipk::step_depth_supported(k); }
     int max_depth() const { return rule_ ? hipk::max_rule_depth() : hipk::max_step_depth(); }
     int blocks_per_cu(int k, u32 flags) const {
+        if (dead_edges()) return hipk::rule_bounded_blocks_per_cu(k, flags);
         return rule_ ? hipk::rule_blocks_per_cu(k, flags) : hipk::step_blocks_per_cu(k, flags);
     }
     int supported_kernel_depth(int want) const {
@@ -432,7 +433,8 @@ class HipEngine : public Engine {
     // that kind's tuned kernel is step_pipe (the interior of a split first pass too, when the full tile's
     // is) and a geometry of depth k exists; else step_temporal where it is instantiated, else the tile
     // kernel (any depth: the bands of a first pass at a step_pipe depth).
-    // Under a rule (rule_: a non-Conway rule, or kernel "rule") every pass of every kind is step_rule.
+    // Under a rule (rule_: a non-Conway rule, kernel "rule", or a bounded board) every pass of every kind is
+    // step_rule, on a bounded board step_rule_bounded (launch).
     enum PassKernel { PK_TEMPORAL, PK_TILE, PK_PIPE, PK_RULE };
     PassKernel pass_kernel(int kind, int k) const {
         if (rule_) return PK_RULE;
@@ -588,7 +590,8 @@ class HipEngine : public Engine {
 
     int dev_ = 0, cus_ = 256;
     std::string kernel_;  // resolved kernel: temporal | tile | lds | rule (auto resolves at init)
-    bool rule_ = false;   // the generic kernel step_rule runs every pass (a non-Conway rule, or kernel "rule")
+    bool rule_ = false;   // the generic kernel step_rule runs every pass (a non-Conway rule, kernel "rule", or a
+                          // bounded board: step_rule_bounded)
     std::string kern_[3];  // per plan kind (full / interior / boundary), resolved by autotune
     int kdepth_ = 8;       // kernel pass depth K (<= halo depth R)
     int tdepth_ = 8;       // temporal-kernel pass depth (the sub-tile mode's, whatever kernel one tile uses)

@@ -90,6 +90,52 @@ std::string canonical_rule(const std::string& r) {
     }
 }
 
+}  // namespace
+
+RleTopology split_rule_topology(const std::string& field) {
+    RleTopology t;
+    const size_t colon = field.find(':');
+    if (colon == std::string::npos) {
+        t.rule = field;
+        return t;
+    }
+    t.rule = field.substr(0, colon);
+    while (!t.rule.empty() && blank(t.rule.back())) t.rule.pop_back();
+    const std::string sfx = field.substr(colon);
+    auto bad = [&](const std::string& why) -> Error {
+        return Error("RLE: header topology suffix '" + sfx + "': " + why);
+    };
+    size_t i = 1;
+    if (i >= sfx.size()) throw bad("expected T<w>[,<h>] or P<w>[,<h>]");
+    const char kind = (char)std::toupper((unsigned char)sfx[i++]);
+    if (kind == 'K' || kind == 'C' || kind == 'S')
+        throw bad(std::string("topology ") + kind + " (Klein bottle, cross-surface, sphere) is not supported; only T (torus) and P (plane)");
+    if (kind != 'T' && kind != 'P') throw bad("unknown topology " + show(sfx[1]) + "; expected T (torus) or P (plane)");
+    auto dimension = [&](const char* name) {
+        if (i >= sfx.size() || !std::isdigit((unsigned char)sfx[i])) throw bad(std::string("expected the board's ") + name);
+        i64 v = 0;
+        for (; i < sfx.size() && std::isdigit((unsigned char)sfx[i]); ++i) {
+            v = v * 10 + (sfx[i] - '0');
+            if (v > kMaxCount) throw bad("number overflow");
+        }
+        if (i < sfx.size() && (sfx[i] == '+' || sfx[i] == '-' || sfx[i] == '*'))
+            throw bad("shifted or twisted edges (+n, -n, *) are not supported");
+        if (v == 0) throw bad(std::string("an infinite ") + name + " (0) is not supported");
+        return v;
+    };
+    t.topology = std::string(1, kind);
+    t.cols = dimension("width");
+    t.rows = t.cols;  // one number: a square board
+    if (i < sfx.size() && sfx[i] == ',') {
+        ++i;
+        t.rows = dimension("height");
+    }
+    if (i < sfx.size()) throw bad("unexpected " + show(sfx[i]) + " after the board's size");
+    return t;
+}
+
+namespace {
+
 void put_run(std::string& out, size_t& line_len, i64 count, char tag) {
     std::string tok = count > 1 ? strprintf("%lld%c", (long long)count, tag) : std::string(1, tag);
     if (line_len + tok.size() > 70) {
@@ -125,7 +171,14 @@ RlePattern parse_rle(const std::string& text) {
     RlePattern p;
     p.rows = hd.y;
     p.cols = hd.x;
-    if (!hd.rule.empty()) p.rule = canonical_rule(hd.rule);
+    if (!hd.rule.empty()) {
+        const RleTopology topo = split_rule_topology(hd.rule);
+        if (topo.rule.empty()) fail("header: empty rule before the topology suffix", i);
+        p.rule = canonical_rule(topo.rule);
+        p.topology = topo.topology;
+        p.bound_cols = topo.cols;
+        p.bound_rows = topo.rows;
+    }
     const i64 nw = p.nw();
     p.words.assign((size_t)(p.rows * nw), 0);
 
@@ -170,7 +223,14 @@ std::string write_rle(const RlePattern& p) {
         throw Error(strprintf("write_rle: a %lld x %lld pattern with %zu words", (long long)p.rows, (long long)p.cols,
                               p.words.size()));
     std::string out = strprintf("x = %lld, y = %lld", (long long)p.cols, (long long)p.rows);
-    if (!p.rule.empty()) out += ", rule = " + p.rule;
+    if (!p.topology.empty()) {
+        if ((p.topology != "T" && p.topology != "P") || p.bound_cols < 1 || p.bound_rows < 1)
+            throw Error(strprintf("write_rle: topology '%s' with a %lld x %lld board (T or P, both sizes >= 1)", p.topology.c_str(),
+                                  (long long)p.bound_rows, (long long)p.bound_cols));
+        out += ", rule = " + (p.rule.empty() ? Rule().str() : p.rule) +
+               strprintf(":%s%lld,%lld", p.topology.c_str(), (long long)p.bound_cols, (long long)p.bound_rows);
+    } else if (!p.rule.empty())
+        out += ", rule = " + p.rule;
     out += '\n';
     size_t line_len = 0;
     const i64 nw = p.nw();

@@ -167,6 +167,7 @@ EngineConfig engine_config(const Options& o, const std::string& backend, int dev
     c.waves_target = o.waves_target;
     c.kernel = env_str("GOL_KERNEL", "auto");
     c.rule = Rule::parse(o.rule.empty() ? env_str("GOL_RULE", "B3/S23") : o.rule);
+    c.boundary = parse_boundary(o.boundary.empty() ? env_str("GOL_BOUNDARY", "torus") : o.boundary);
     c.tile_waves = (int)env_int("GOL_TILE_WAVES", 8);
     c.tune_tile_waves = getenv("GOL_TILE_WAVES") == nullptr;
     c.transport = (o.transport == "rccl" || o.transport == "p2p") ? "device" : o.transport;
@@ -319,6 +320,7 @@ void save_checkpoint(Engine& eng, const std::string& prefix, u64 seed) {
         hd.generation = eng.generation();
         hd.seed = seed;
         hd.reserved[0] = eng.config().rule.code();  // birth | survive << 16 (0, older files: B3/S23)
+        hd.reserved[1] = (u64)eng.config().boundary;  // 0 torus (and every older file), 1 dead
         const int fd = open(tmp.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
         ok = fd >= 0 && ftruncate(fd, (off_t)(sizeof(hd) + (size_t)(g.dec.H * gw) * 8)) == 0 &&
              pwrite(fd, &hd, sizeof(hd), 0) == (ssize_t)sizeof(hd);
@@ -382,6 +384,12 @@ u64 load_checkpoint(Engine& eng, const std::string& prefix) {
             throw Error("checkpoint " + name + " was written under rule " + theirs.str() + ", this run has " +
                         mine.str());
         }
+        // (the boundary likewise, on every rank before anything collective)
+        if (hd.reserved[1] > 1)
+            throw Error(strprintf("checkpoint %s names an unknown boundary (%llu)", name.c_str(), (unsigned long long)hd.reserved[1]));
+        if ((Boundary)hd.reserved[1] != eng.config().boundary)
+            throw Error("checkpoint " + name + " was written on a board with boundary " + boundary_name((Boundary)hd.reserved[1]) +
+                        ", this run has boundary " + boundary_name(eng.config().boundary));
         std::vector<u64> words((size_t)(g.h * nw));
         const off_t base = (off_t)sizeof(CkptHeader);
         if (nw == gw) {
@@ -436,6 +444,7 @@ void write_metrics(const Options& o, Engine& eng, const CliArgs& a, double durat
     f << "  \"graph_launches\": " << s.graph_launches << ",\n";
     f << "  \"kernel\": \"" << s.kernel << "\",\n";
     f << "  \"rule\": \"" << s.rule << "\",\n";
+    f << "  \"boundary\": \"" << s.boundary << "\",\n";
     f << "  \"schedule\": \"" << s.schedule << "\",\n";
     f << "  \"autotune\": \"" << s.tuning << "\",\n";
     f << "  \"plan_waves\": " << s.plan_waves << ",\n  \"lane_efficiency\": " << s.lane_efficiency << ",\n";
@@ -473,6 +482,16 @@ CliPattern load_cli_pattern(Options& o) {
         else if (Rule::parse(env) != Rule::parse(cp.p.rule))
             throw Error("GOL_PATTERN_FILE " + o.pattern_file + " names rule " + cp.p.rule + ", GOL_RULE asks for " +
                         Rule::parse(env).str());
+    }
+    // the file's topology likewise (its size is ignored: worldSize governs): P is a bounded board, T the torus
+    if (!cp.p.topology.empty()) {
+        const std::string file_b = cp.p.topology == "P" ? "dead" : "torus";
+        const std::string env = env_str("GOL_BOUNDARY", "");
+        if (env.empty())
+            o.boundary = file_b;
+        else if (parse_boundary(env) != parse_boundary(file_b))
+            throw Error("GOL_PATTERN_FILE " + o.pattern_file + " names topology " + cp.p.topology + " (boundary " + file_b +
+                        "), GOL_BOUNDARY asks for " + env);
     }
     return cp;
 }
@@ -561,6 +580,11 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
             out.rows = dec.H;
             out.cols = dec.W;
             out.rule = eng->config().rule.str();
+            if (eng->config().boundary == Boundary::Dead) {  // the whole bounded board: its plane goes into the header
+                out.topology = "P";
+                out.bound_cols = dec.W;
+                out.bound_rows = dec.H;
+            }
             const std::vector<u8> cells = eng->window(0, 0, dec.H, dec.W);  // collective
             if (rank == 0) {
                 out.words.assign((size_t)(out.rows * out.nw()), 0);
@@ -595,6 +619,7 @@ int run_cli(int argc, char** argv) {
         // GOL_RULE (read again per rank in engine_config, beside GOL_KERNEL): a bad value ends the job here,
         // with the parse error, before any rank starts
         (void)Rule::parse(env_str("GOL_RULE", "B3/S23"));  // (GOL_VERBOSE=1: describe() names the rule)
+        (void)parse_boundary(env_str("GOL_BOUNDARY", "torus"));  // GOL_BOUNDARY likewise
         // GOL_PATTERN_FILE likewise: an unreadable file, or one whose rule GOL_RULE contradicts, ends the job here
         const CliPattern cp = load_cli_pattern(o);
         LaunchInfo li = detect_launch(o);

@@ -59,6 +59,11 @@ class Simulation:
     decomp/grid:  ``"1d"`` row strips (reference) or ``"2d"`` blocks, optional ``"PxxPy"`` grid.
     width:        board columns (0 = N: the reference's square tiles).  With ``width`` the per-rank
                   strip (or, in global mode, the board) is N rows x ``width`` columns.
+    boundary:     ``"torus"`` (default, the reference) or ``"dead"``: a bounded board, every cell outside
+                  ``[0, H) x [0, W)`` dead in every generation (GOL_BOUNDARY).  HIP: the bounded rule kernel
+                  ``step_rule_bounded`` for every rule, B3/S23 included (generic-kernel speed); without
+                  ``compat``, ``subtiles=2`` or the torus-only kernels.  Windows and stamps must lie inside
+                  a bounded board.
     compat:       reproduce the reference's halo quirks (frozen gen-0 halos, P<=2 swap).
     watchdog:     seconds without progress before the job is aborted (0 = off; GOL_WATCHDOG).
     """
@@ -93,6 +98,7 @@ class Simulation:
         width: int = 0,
         subtile_overlap: Optional[int] = None,
         rule: str = os.environ.get("GOL_RULE", "B3/S23"),
+        boundary: Optional[str] = None,
     ):
         self.transport = transport if transport is not None else _gol.SelfTransport()
         P, rank = self.transport.size(), self.transport.rank()
@@ -115,6 +121,16 @@ class Simulation:
                 raise ValueError(f"subtiles=2 runs B3/S23 only, not rule {cfg.rule}")
             if self.backend == "hip" and kernel in ("temporal", "tile", "pipe", "resident", "lds"):
                 raise ValueError(f"kernel {kernel!r} implements B3/S23 only, not rule {cfg.rule}")
+        if boundary is None:  # (read per call, so a test or a driver can set it between simulations)
+            boundary = os.environ.get("GOL_BOUNDARY", "torus")
+        cfg.boundary = boundary  # (ValueError on anything but torus or dead, naming it)
+        if cfg.boundary == "dead":
+            if compat:
+                raise ValueError("compat=True with boundary dead: the reference is a torus")
+            if int(subtiles) == 2:
+                raise ValueError("subtiles=2 implements the torus only, not boundary dead")
+            if self.backend == "hip" and kernel in ("temporal", "tile", "pipe", "resident", "lds"):
+                raise ValueError(f"kernel {kernel!r} implements the torus only, not boundary dead")
         cfg.subtiles = int(subtiles)  # 2 / 0 / -1 auto: two sub-tiles per rank on two streams (HIP, 1-D)
         cfg.run_hint = int(run_hint)  # generations of the runs to come: one replay graph covers them
         cfg.rows_per_wave = rows_per_wave
@@ -194,12 +210,23 @@ class Simulation:
         return self.engine.describe()
 
     # -- views and patterns ----------------------------------------------------------------
-    # Global board coordinates on the torus; all of these are collective, and every rank gets the same result.
+    # Global board coordinates (on the torus they wrap; on a bounded board a rectangle lies inside the board); all of
+    # these are collective, and every rank gets the same result.
     def window(self, r0: int, c0: int, rows: int, cols: int) -> np.ndarray:
         """``rows x cols`` cells of the global board from ``(r0, c0)`` on as a uint8 array.  The window may
         start anywhere (coordinates wrap), cross the board's seams and any rank boundary; it is at most the
-        board's size.  On the HIP backend only the window's bytes leave the device."""
+        board's size.  On a bounded board (``boundary="dead"``) it must lie inside the board.  On the HIP backend
+        only the window's bytes leave the device."""
+        self._check_inside("window", int(r0), int(c0), int(rows), int(cols))
         return self.engine.window(int(r0), int(c0), int(rows), int(cols))
+
+    def _check_inside(self, what: str, r0: int, c0: int, rows: int, cols: int) -> None:
+        """On a bounded board a rectangle must lie inside the board (nothing wraps); every rank raises alike."""
+        H, W = self.decomposition.H, self.decomposition.W
+        if self.config.boundary == "dead" and (r0 < 0 or c0 < 0 or r0 + rows > H or c0 + cols > W):
+            raise ValueError(
+                f"{what}: the {rows} x {cols} rectangle at ({r0}, {c0}) does not lie inside the bounded {H} x {W} board"
+            )
 
     def density(self, block_rows: int, block_cols: Optional[int] = None) -> np.ndarray:
         """Live cells per ``block_rows x block_cols`` block of the global board: a uint32 array of
@@ -231,7 +258,8 @@ class Simulation:
         """Combine a pattern (an RLE path, RLE text or a 2-D 0/1 array) with the live board, its first cell at
         ``at = (row, col)`` or centred.  ``mode``: ``"or"``, ``"replace"`` (the pattern's bounding rectangle is
         overwritten), ``"xor"`` or ``"clear"`` (cells die where the pattern is live).  The pattern may cross
-        the seams and rank boundaries; one larger than the board is refused, and so is ``compat`` mode."""
+        the seams and rank boundaries (on a bounded board it must lie inside the board); one larger than the
+        board is refused, and so is ``compat`` mode."""
         p = self._pattern(pattern)
         if mode not in ("or", "replace", "xor", "clear"):
             raise ValueError(f"stamp mode must be or, replace, xor or clear, got {mode!r}")
@@ -244,6 +272,7 @@ class Simulation:
             if at != "center":
                 raise ValueError(f"at must be (row, col) or 'center', got {at!r}")
             at = ((H - p.rows) // 2, (W - p.cols) // 2)
+        self._check_inside("stamp", int(at[0]), int(at[1]), p.rows, p.cols)
         self.engine.stamp(p, int(at[0]), int(at[1]), mode)
         return self
 
@@ -253,24 +282,57 @@ class Simulation:
         p = self._pattern(path)
         if p.rule and p.rule != self.config.rule:
             raise ValueError(f"the RLE pattern names rule {p.rule}, this simulation runs {self.config.rule}")
+        if p.topology and self._topology_boundary(p.topology) != self.config.boundary:
+            raise ValueError(
+                f"the RLE pattern names topology {p.topology} (boundary {self._topology_boundary(p.topology)}), "
+                f"this simulation runs boundary {self.config.boundary}"
+            )
         self.init(0)
         return self.stamp(p, at=at, mode="or")
 
+    @staticmethod
+    def _topology_boundary(topology: str) -> str:
+        """The boundary an RLE header's topology suffix stands for: P (plane) is dead edges, T the torus."""
+        return "dead" if topology == "P" else "torus"
+
     def save_rle(self, path, window=None) -> None:
         """Write ``window = (r0, c0, rows, cols)`` (default: the whole board) as an RLE file with the
-        simulation's rule.  Collective; rank 0 writes."""
+        simulation's rule.  The whole board of a bounded simulation also names its plane in the header
+        (``rule = B3/S23:P<W>,<H>``).  Collective; rank 0 writes."""
         from ..ops.rle import pattern_from_cells
 
-        r0, c0, rows, cols = window if window is not None else (0, 0, self.decomposition.H, self.decomposition.W)
+        H, W = self.decomposition.H, self.decomposition.W
+        r0, c0, rows, cols = window if window is not None else (0, 0, H, W)
         cells = self.window(r0, c0, rows, cols)
         if self.geometry.rank == 0:
-            _gol.write_rle_file(os.fspath(path), pattern_from_cells(cells, self.config.rule))
+            if window is None and self.config.boundary == "dead":
+                p = pattern_from_cells(cells, self.config.rule, "P", W, H)
+            else:
+                p = pattern_from_cells(cells, self.config.rule)
+            _gol.write_rle_file(os.fspath(path), p)
 
     @classmethod
-    def from_rle(cls, path, N: int, *, at="center", **kw) -> "Simulation":
+    def from_rle(cls, path, N: Optional[int] = None, *, at="center", **kw) -> "Simulation":
         """A simulation of side ``N`` under the file's rule (the default rule when it names none) with the
-        file's pattern on an otherwise empty board."""
+        file's pattern on an otherwise empty board.  A topology suffix in the file's rule field
+        (``:P<w>,<h>`` plane = dead edges, ``:T<w>,<h>`` torus) sets the boundary unless the call does, and
+        without ``N`` the board is the suffix's ``h`` rows x ``w`` columns."""
         p = cls._pattern(path)
+        if p.topology:
+            file_b = cls._topology_boundary(p.topology)
+            if kw.get("boundary") is not None:
+                c = _gol.EngineConfig()
+                c.boundary = kw["boundary"]
+                if c.boundary != file_b:
+                    raise ValueError(
+                        f"RLE file {path!r} names topology {p.topology} (boundary {file_b}), the call asks for {c.boundary}"
+                    )
+            kw["boundary"] = file_b
+        if N is None:
+            if not p.topology:
+                raise ValueError(f"from_rle without N needs a board size in the file: {path!r} has no topology suffix")
+            N = p.bound_rows
+            kw.setdefault("width", p.bound_cols)
         if p.rule:
             if "rule" in kw:
                 c = _gol.EngineConfig()

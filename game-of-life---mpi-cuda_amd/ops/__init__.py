@@ -5,6 +5,7 @@ from .oracle import (  # noqa: F401
     initial_board,
     numpy_step,
     numpy_step_rule,
+    numpy_step_rule_bounded,
     parse_rule,
     quirk_model,
     random_board,

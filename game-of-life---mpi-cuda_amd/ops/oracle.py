@@ -5,6 +5,8 @@
   (PyTorch-ROCm) to cross-check large boards independently of the HIP kernels.
 * :func:`numpy_step_rule` / :func:`torch_step_rule` — the same two for any life-like rule ``B.../S...``,
   with a rule parser of their own (independent of the native one).
+* :func:`numpy_step_rule_bounded` — a life-like rule on a bounded board (dead cells beyond the edges), from a
+  zero-padded neighbour count, written without the torus oracle.
 * :func:`quirk_model` — the reference's actual behaviour (survey Q1-Q3): every rank steps its tile
   with x-wrap and CONSTANT ghost rows taken from the generation-0 boards, with the P <= 2 swap.
 * :func:`initial_board` — pattern placement mirror (patterns 0-5) computed in Python, including the
@@ -103,6 +105,27 @@ def numpy_step_rule(board: np.ndarray, rule, generations: int = 1) -> np.ndarray
             if dy or dx
         )
         b = lut[b, n]
+    return b
+
+
+def numpy_step_rule_bounded(board: np.ndarray, rule, generations: int = 1) -> np.ndarray:
+    """Byte-per-cell step of a life-like rule on a bounded board: every cell outside the array is dead in every
+    generation.  Written on its own, from a neighbour count over a zero-padded copy (no roll, no torus oracle)."""
+    birth, survive = parse_rule(rule)
+    b = np.asarray(board, dtype=np.uint8)
+    if b.ndim != 2:
+        raise ValueError(f"a board is a 2-D array, got shape {b.shape}")
+    H, W = b.shape
+    for _ in range(generations):
+        pad = np.zeros((H + 2, W + 2), dtype=np.int32)
+        pad[1:-1, 1:-1] = b
+        n = np.zeros((H, W), dtype=np.int32)
+        for dy in (0, 1, 2):
+            for dx in (0, 1, 2):
+                if dy != 1 or dx != 1:
+                    n += pad[dy : dy + H, dx : dx + W]
+        alive = b == 1
+        b = np.where(alive, (survive >> n) & 1, (birth >> n) & 1).astype(np.uint8)
     return b
 
 

@@ -8,8 +8,9 @@ from .._native import _gol
 from .bitpack import pack_cells, unpack_words
 
 
-def pattern_from_cells(cells, rule: str = ""):
-    """A 2-D 0/1 array -> native ``RlePattern`` (``rule``: any form the engine's rule parser takes, or "")."""
+def pattern_from_cells(cells, rule: str = "", topology: str = "", bound_cols: int = 0, bound_rows: int = 0):
+    """A 2-D 0/1 array -> native ``RlePattern`` (``rule``: any form the engine's rule parser takes, or "";
+    ``topology``: "" or the header suffix's "T" / "P" with the board it names)."""
     cells = np.asarray(cells)
     if cells.ndim != 2 or cells.shape[0] < 1 or cells.shape[1] < 1:
         raise ValueError(f"a pattern is a 2-D array with at least one cell, got shape {cells.shape}")
@@ -17,7 +18,7 @@ def pattern_from_cells(cells, rule: str = ""):
         from .oracle import parse_rule, rule_string
 
         rule = rule_string(parse_rule(rule))
-    return _gol.RlePattern(pack_cells(cells != 0), int(cells.shape[1]), rule)
+    return _gol.RlePattern(pack_cells(cells != 0), int(cells.shape[1]), rule, topology, int(bound_cols), int(bound_rows))
 
 
 def pattern_cells(pattern) -> np.ndarray:
