@@ -43,7 +43,10 @@ void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, co
 // k generations (k <= L.R).  Ping-pongs between a and b; returns the buffer with the result.  On a bounded
 // board the input rows [-k, h + k) of `a` are masked in place first (the ghost rows and words hold what the
 // torus machinery delivered across the board's edges), then every generation's output.
-u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule = Rule(), const Edges& edges = Edges());
+// counts (census; k slots, or null): counts[g] += the live cells of the tile itself after generation g + 1: rows
+// [0, h), words [0, nw) under the storage mask, no ghost row or word.
+u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule = Rule(), const Edges& edges = Edges(),
+               u64* counts = nullptr);
 
 // x-periodic ghost words (and tail ghost bits) for rows [r_lo, r_hi).
 void fill_ghost_cols_wrap(u64* buf, const Layout& L, i64 r_lo, i64 r_hi);

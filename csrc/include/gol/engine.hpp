@@ -58,6 +58,9 @@ struct EngineConfig {
                                       // dead in every generation (GOL_BOUNDARY).  The torus machinery (ghost
                                       // fills, exchanges with the wrap-around neighbour) keeps running; what it
                                       // delivers across a global edge is masked away.  HIP: step_rule_bounded
+    bool census = false;              // census mode (GOL_CENSUS): every generation run() computes also yields the
+                                      // global live-cell count of that generation (Engine::census).  HIP: the
+                                      // census kernel step_census runs every pass, for every rule and boundary
     int tile_waves = 8;               // tile kernel: waves per workgroup (4, 8, 16)
     bool tune_tile_waves = true;      // GOL_KERNEL=auto may also try 8 waves (false: GOL_TILE_WAVES set)
     std::string transport = "auto";   // auto | device | host  (host = stage halos through host memory)
@@ -106,6 +109,7 @@ struct EngineStats {
     std::string kernel;        // stencil kernel in use (HIP: temporal | tile | lds | rule@K; CPU: cpu)
     std::string rule;          // the rule, canonical (B3/S23)
     std::string boundary;      // torus | dead
+    bool census = false;       // census mode
     std::string schedule;      // superstep schedule: local (no neighbours) | split | full
     std::string tuning;        // init-time measurements behind the auto choices (HIP)
     bool registered = false;   // HIP + RCCL: the boards are registered with the communicator (zero-copy halos)
@@ -136,6 +140,17 @@ class Engine {
     // Global values (collective over the transport).
     u64 population();
     u64 fingerprint();
+
+    // ----- census (EngineConfig::census) -----
+    // Collective: (start, counts), counts[i] the GLOBAL population at generation start + 1 + i, for every
+    // generation run() has computed since the record was cleared: by init() (start 0), by a checkpoint restore
+    // (start: the restored generation) or by census_clear() (start: the generation reached).  stamp() and
+    // set_tile_words() leave it alone: the generation count runs on.  The same on every rank (the ranks' series
+    // are summed over the control plane: gatherv to rank 0, broadcast).  Throws, before any communication, on an
+    // engine that is not in census mode.
+    std::pair<u64, std::vector<u64>> census();
+    void census_clear();
+    void census_restart(u64 generation);  // an empty record that starts at `generation` (load_checkpoint)
 
     // ----- views and pattern stamping -----
     // Global board coordinates on the torus: a window or a pattern may start anywhere (r0, c0 are taken
@@ -267,6 +282,13 @@ class Engine {
         }
         Watchdog* w_;
     };
+
+    // Census record of this rank: the counts already on the host; a backend that keeps counts elsewhere (HIP: a
+    // device buffer the kernels add into) appends them in census_collect() and drops them in census_discard().
+    virtual void census_collect() {}
+    virtual void census_discard() {}
+    std::vector<u64> census_host_;
+    u64 census_start_ = 0;
 
     Geometry g_;
     EngineConfig cfg_;

@@ -9,6 +9,8 @@
 //                       B.../S... from two run-time masks (rule_kernel.hip; K = 1..8).
 //   step_rule_bounded<K> — step_rule on a bounded board (dead cells beyond the global edges): the loaded row and
 //                       every level masked to the board's cells (rule_bounded_kernel.hip; K = 1..8).
+//   step_census<K>    — step_rule / step_rule_bounded that also counts the tile's live cells after every generation
+//                       of the pass: a masked v_bcnt per level, K atomics per wave (census_kernel.hip; K = 1..8).
 //   step_lds          — single-generation LDS-tiled variant (tile + ghost words staged in LDS);
 //                       kept as a measured alternative (GOL_KERNEL=lds).
 //   fill_ghost_cols   — x-periodic ghost words for widths that are not a multiple of 64.
@@ -96,6 +98,19 @@ struct BoardEdges {
 int rule_bounded_blocks_per_cu(int k, u32 flags);
 void launch_step_rule_bounded(int k, const Rule& rule, const BoardEdges& edges, const u64* src, u64* dst,
                               const LaneDesc* plan, i64 n_waves, const StepParams& p, hipStream_t s);
+// step_census<K> (census_kernel.hip): step_rule (edges == nullptr: the torus) or step_rule_bounded (edges) that also
+// adds the live cells of the tile after generation g + 1 of the pass's k to the slot at counts + g * kCensusSlotWords
+// (device memory, 64-bit atomics; nullptr: count nothing).  A slot is kCensusStripes partial sums kCensusStripeWords
+// words apart (a 128-byte line each); the generation's count is their sum.  Every cell of the tile (tile_cols
+// columns, p.h rows) is counted once per generation over the launches whose plans partition a pass's output
+// region.  Same plans, StepParams, rows and words read and written, and the same argument checks, as
+// launch_step_rule_bounded.  Depths 1 .. max_census_depth().
+constexpr int kCensusStripes = 16, kCensusStripeWords = 16;
+constexpr int kCensusSlotWords = kCensusStripes * kCensusStripeWords;  // u64 words from one generation's slot to the next
+int max_census_depth();
+int census_blocks_per_cu(int k, u32 flags, bool bounded);
+void launch_step_census(int k, const Rule& rule, const BoardEdges* edges, i64 tile_cols, const u64* src, u64* dst,
+                        const LaneDesc* plan, i64 n_waves, const StepParams& p, u64* counts, hipStream_t s);
 // LDS-resident temporal kernel (step_tile): one workgroup of `nw_per_wg` (4, 8, 16) waves per plan
 // wave; `rows` = the plan's rows per chunk (<= tile_max_rows(k), the 160 KiB LDS limit).
 constexpr size_t kMaxLdsBytes = 160 * 1024;

@@ -16,6 +16,7 @@
 #include "gol/config.hpp"
 #include "gol/cpu.hpp"
 #include "gol/engine.hpp"
+#include "gol/hip_kernels.hpp"
 #include "gol/io.hpp"
 #include "gol/pattern.hpp"
 #include "gol/plan.hpp"
@@ -108,6 +109,7 @@ py::dict stats_dict(const EngineStats& s) {
     d["kernel"] = s.kernel;
     d["rule"] = s.rule;
     d["boundary"] = s.boundary;
+    d["census"] = s.census;
     d["schedule"] = s.schedule;
     d["kernel_depth"] = s.kernel_depth;
     d["tile_waves"] = s.tile_waves;
@@ -271,6 +273,7 @@ PYBIND11_MODULE(_gol, m) {
         .def_readwrite("kernel_depth", &EngineConfig::kernel_depth)
         .def_readwrite("graph_rccl", &EngineConfig::graph_rccl)
         .def_readwrite("plan_xcds", &EngineConfig::plan_xcds)
+        .def_readwrite("census", &EngineConfig::census)
         // the life-like rule as a string (any form Rule::parse takes; reads back canonical, B3/S23)
         .def_property(
             "rule", [](const EngineConfig& c) { return c.rule.str(); },
@@ -331,6 +334,19 @@ PYBIND11_MODULE(_gol, m) {
         .def("local_reduce", &Engine::local_reduce, py::call_guard<py::gil_scoped_release>())
         .def("population", &Engine::population, py::call_guard<py::gil_scoped_release>())
         .def("fingerprint", &Engine::fingerprint, py::call_guard<py::gil_scoped_release>())
+        // census mode (collective): (start, counts), counts[i] the global population at generation start + 1 + i
+        .def("census",
+             [](Engine& e) {
+                 std::pair<u64, std::vector<u64>> c;
+                 {
+                     py::gil_scoped_release r;
+                     c = e.census();
+                 }
+                 py::array_t<u64> a((py::ssize_t)c.second.size());
+                 if (!c.second.empty()) std::memcpy(a.mutable_data(), c.second.data(), c.second.size() * sizeof(u64));
+                 return py::make_tuple(c.first, a);
+             })
+        .def("census_clear", &Engine::census_clear, py::call_guard<py::gil_scoped_release>())
         // views and stamping (collective; global board coordinates on the torus)
         .def(
             "window",
@@ -492,6 +508,7 @@ PYBIND11_MODULE(_gol, m) {
     // ---- devices / bench ------------------------------------------------------------------
     m.def("hip_device_count", []() { return hip_device_count(nullptr); });
     m.def("hip_set_device", &hip_set_device);
+    m.def("max_census_depth", []() { return hipk::max_census_depth(); });  // deepest pass of the census kernel
     m.def(
         "naive_byte_run",
         [](i64 N, int gens, int threads, bool sync_each, u64 seed) {

@@ -113,7 +113,7 @@ void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, co
     }
 }
 
-u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges) {
+u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges, u64* counts) {
     if (k < 1 || k > L.R) throw Error(strprintf("superstep depth %d outside 1..%d", k, L.R));
     u64* src = a;
     u64* dst = b;
@@ -121,6 +121,7 @@ u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const E
     for (int g = 0; g < k; ++g) {
         i64 ext = k - 1 - g;
         step_rows(src, dst, L, -ext, L.h + ext, rule, edges);
+        if (counts) counts[g] += population(dst, L);  // the tile's own cells: rows [0, h), words [0, nw), no ghosts
         std::swap(src, dst);
     }
     return src;

@@ -43,6 +43,14 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
                 if (cfg_.kernel == k)
                     throw Error("kernel '" + cfg_.kernel + "' implements the torus only, not boundary dead (use kernel auto or rule)");
     }
+    if (cfg_.census) {
+        if (cfg_.compat) throw Error("census with GOL_COMPAT=reference: compat mode runs the reference's loop, not the census kernel");
+        if (cfg_.subtiles == 2) throw Error("two sub-tiles per rank (GOL_SUBTILES=2) do not run the census kernel");
+        if (cfg_.backend == "hip")
+            for (const char* k : {"temporal", "tile", "pipe", "resident", "lds"})
+                if (cfg_.kernel == k)
+                    throw Error("kernel '" + cfg_.kernel + "' counts no census: the census kernel runs every pass (use kernel auto or rule)");
+    }
     if (t_->size() != g_.dec.P || t_->rank() != g_.rank)
         throw Error(strprintf("transport (rank %d of %d) does not match the geometry (rank %d of %d)", t_->rank(),
                               t_->size(), g_.rank, g_.dec.P));
@@ -70,7 +78,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     const bool sub_tall = cfg_.backend == "hip" && (cfg_.subtiles == 2 || cfg_.subtiles < 0) && !two_d() && strip_rows >= kSubtileMinRows &&
                           g_.dec.W % 64 == 0 && !cfg_.force_split && !cfg_.profile && !cfg_.compat &&
                           cfg_.kernel != "lds" && cfg_.kernel != "tile" && cfg_.kernel != "pipe" &&
-                          cfg_.kernel != "rule" && cfg_.rule.is_conway() && !dead_edges();
+                          cfg_.kernel != "rule" && cfg_.rule.is_conway() && !dead_edges() && !cfg_.census;
     // (1-D strips with neighbours: 128 measured 1-3% faster than 64 through RCCL self-exchange,
     // 4096 x 32768 2.44 -> 2.36, 8192 x 65536 5.93 -> 5.85 us/gen; profiles/per_rank_tiles_self_exchange.txt)
     const int want = cfg_.halo_depth > 0 ? cfg_.halo_depth : (sub_tall || tall_strips ? 128 : (tall_tiles ? 56 : 32));
@@ -84,6 +92,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     stats_.depth = R;
     stats_.rule = cfg_.rule.str();
     stats_.boundary = boundary_name(cfg_.boundary);
+    stats_.census = cfg_.census;
     std::string f = env_str("GOL_FAULT", "");
     if (!f.empty()) {
         int fr = -1;
@@ -184,14 +193,20 @@ void Engine::init(const PatternSpec& p) {
     stats_.kernel_depth = L_.R;
     stats_.rule = cfg_.rule.str();
     stats_.boundary = boundary_name(cfg_.boundary);
+    stats_.census = cfg_.census;
+    census_restart(0);
     if (t_->size() > 1) {
-        // every rank must run the same rule on the same boundary: agreed like the schedule, by reductions every
-        // rank sees (so on a mismatch every rank raises and none waits for a peer).  One code: the rule's 32 bits,
-        // the boundary above them (exact in a double).
-        const double code = (double)cfg_.rule.code() + (double)((u64)cfg_.boundary << 32);
+        // every rank must run the same rule on the same boundary, in the same census mode: agreed like the schedule,
+        // by reductions every rank sees (so on a mismatch every rank raises and none waits for a peer).  One code:
+        // the rule's 32 bits, the boundary above them, the census mode above that (exact in a double).
+        const double code = (double)cfg_.rule.code() + (double)((u64)cfg_.boundary << 32) + (double)((u64)cfg_.census << 40);
         const double lo = t_->allreduce_min(code), hi = t_->allreduce_max(code);
         if (lo != hi) {
-            const u64 ulo = (u64)lo, uhi = (u64)hi;
+            const u64 clo = (u64)lo, chi = (u64)hi;
+            if ((clo >> 40) != (chi >> 40))
+                throw Error(strprintf("the ranks disagree on the census mode: rank %d has census %s (some ranks on, some off)",
+                                      g_.rank, cfg_.census ? "on" : "off"));
+            const u64 ulo = clo & 0xFFFFFFFFFFull, uhi = chi & 0xFFFFFFFFFFull;
             if ((ulo >> 32) != (uhi >> 32))
                 throw Error(strprintf("the ranks disagree on the boundary: rank %d has %s (%s .. %s over the ranks)", g_.rank,
                                       stats_.boundary.c_str(), boundary_name((Boundary)(ulo >> 32)),
@@ -274,6 +289,51 @@ std::vector<double> Engine::time_runs(u64 gens, int reps) {
 
 u64 Engine::population() { return t_->allreduce_sum(local_reduce().first); }
 u64 Engine::fingerprint() { return t_->allreduce_sum(local_reduce().second); }
+
+// ---------------------------------------------------------------------------------------------
+// Census (the backends fill census_host_ with this rank's counts; the sum over the ranks is made here)
+// ---------------------------------------------------------------------------------------------
+
+std::pair<u64, std::vector<u64>> Engine::census() {
+    if (!cfg_.census)
+        throw Error("census(): this engine is not in census mode (EngineConfig::census, Simulation(census=True), GOL_CENSUS=1)");
+    census_collect();
+    std::vector<u64> out = census_host_;
+    if (t_->size() == 1) return {census_start_, out};
+    // (every rank ran the same generations: the series have one length, checked on rank 0, which tells the others)
+    const size_t n = out.size();
+    std::vector<std::vector<u8>> all;
+    t_->gatherv(out.data(), n * sizeof(u64), &all, 0);
+    u64 ok = 1;
+    if (g_.rank == 0)
+        for (int q = 1; q < t_->size(); ++q) {
+            if (all[(size_t)q].size() != n * sizeof(u64)) {
+                ok = 0;
+                break;
+            }
+            u64 part = 0;
+            for (size_t i = 0; i < n; ++i) {
+                memcpy(&part, all[(size_t)q].data() + i * sizeof(u64), sizeof(u64));
+                out[i] += part;
+            }
+        }
+    t_->broadcast(&ok, sizeof(ok), 0);
+    if (!ok) throw Error("census: the ranks' series differ in length (every rank must run the same generations)");
+    if (n > 0) t_->broadcast(out.data(), n * sizeof(u64), 0);
+    return {census_start_, out};
+}
+
+void Engine::census_clear() {
+    if (!cfg_.census) throw Error("census_clear(): this engine is not in census mode");
+    census_collect();
+    census_restart(census_start_ + (u64)census_host_.size());
+}
+
+void Engine::census_restart(u64 generation) {
+    census_discard();
+    census_host_.clear();
+    census_start_ = generation;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Views and pattern stamping (collective wrappers; the backends do the rank-local part)
@@ -534,7 +594,12 @@ class CpuEngine : public Engine {
             exchange(k);
             if (self_y()) cpu::fill_ghost_rows_wrap(cur_, L_);
         }
-        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, cpu::Edges(cfg_.boundary, g_));
+        u64* counts = nullptr;
+        if (cfg_.census) {  // this rank's own cells after each of the k generations
+            census_host_.resize(census_host_.size() + (size_t)k, 0);
+            counts = census_host_.data() + (census_host_.size() - (size_t)k);
+        }
+        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, cpu::Edges(cfg_.boundary, g_), counts);
         if (res != cur_) std::swap(cur_, oth_);
         if (self_x()) cpu::fill_ghost_cols_wrap(cur_, L_, 0, L_.h);
     }

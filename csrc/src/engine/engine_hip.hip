@@ -41,7 +41,11 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
     // A non-Conway rule, or kernel "rule" (B3/S23 through the generic kernel: its cross-check), runs step_rule
     // in every pass of every plan kind.  (Engine::Engine refused the specialised kernels with such a rule.)
     // A bounded board runs step_rule_bounded, for every rule including B3/S23 (there is no bounded step_temporal).
-    rule_ = kernel_ == "rule" || !cfg_.rule.is_conway() || dead_edges();
+    // Census mode runs step_census, likewise for every rule and either boundary.
+    rule_ = kernel_ == "rule" || !cfg_.rule.is_conway() || dead_edges() || cfg_.census;
+    if (cfg_.census && cfg_.kernel_depth > hipk::max_census_depth())
+        throw Error(strprintf("census: kernel_depth %d exceeds the census kernel's deepest pass, %d generations (GOL_KERNEL_DEPTH)",
+                              cfg_.kernel_depth, hipk::max_census_depth()));
     if (rule_ && kernel_ == "auto") kernel_ = "rule";  // (any other name is refused below)
     hipk::ensure_trash();  // before any launch or graph capture
     // Kernel pass depth K (generations per HBM pass) vs halo depth R (generations per
@@ -219,7 +223,7 @@ HipEngine::~HipEngine() {
     for (void* q : {(void*)res_status_, (void*)res_scratch_[0], (void*)res_scratch_[1]})
         if (q) hipFree(q);
     for (void* p : deferred_free_) hipFree(p);
-    for (void* p : {(void*)d_view_, (void*)d_grid_, (void*)d_pat_})
+    for (void* p : {(void*)d_view_, (void*)d_grid_, (void*)d_pat_, (void*)d_census_})
         if (p) hipFree(p);
     if (h_view_) hipHostFree(h_view_);
     hipFree(d_red_);
@@ -274,7 +278,67 @@ void HipEngine::set_tile_words(const std::vector<u64>& dense) {
     synchronize();
 }
 
+// Census mode: the call's counts go to device slots reserved here (census_begin), in chunks of at most
+// kCensusMaxSlots generations; the kernels find their slot through census_at_ (tile_superstep, launch).
 void HipEngine::run(u64 generations) {
+    if (!cfg_.census || census_mute_) return run_counted(generations);
+    while (generations > 0) {
+        const u64 n = std::min<u64>(generations, kCensusMaxSlots);
+        census_begin(n);
+        census_at_ = d_census_ + census_dev_n_ * hipk::kCensusSlotWords;
+        try {
+            run_counted(n);
+        } catch (...) {
+            census_at_ = nullptr;
+            throw;
+        }
+        census_at_ = nullptr;
+        census_dev_n_ += (size_t)n;
+        generations -= n;
+    }
+}
+
+void HipEngine::census_begin(u64 generations) {
+    const size_t n = (size_t)generations;
+    if (census_dev_n_ + n <= census_cap_) return;
+    census_collect();  // (synchronises; leaves the buffer empty and zeroed)
+    if (n <= census_cap_) return;
+    synchronize();
+    if (d_census_) deferred_free_.push_back(d_census_);
+    d_census_ = nullptr;
+    census_cap_ = 0;
+    const size_t cap = std::max<size_t>(n, 1024);
+    HIP_CHECK(hipMalloc(&d_census_, cap * kCensusSlotBytes));
+    census_cap_ = cap;
+    HIP_CHECK(hipMemsetAsync(d_census_, 0, cap * kCensusSlotBytes, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+}
+
+void HipEngine::census_collect() {
+    if (census_dev_n_ == 0) return;
+    synchronize();  // the passes of either stream have added their counts
+    std::vector<u64> raw(census_dev_n_ * (size_t)hipk::kCensusSlotWords);
+    HIP_CHECK(hipMemcpyAsync(raw.data(), d_census_, raw.size() * sizeof(u64), hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(hipMemsetAsync(d_census_, 0, census_dev_n_ * kCensusSlotBytes, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    for (size_t g = 0; g < census_dev_n_; ++g) {  // a generation's count: the sum of its slot's stripes
+        u64 sum = 0;
+        for (int st = 0; st < hipk::kCensusStripes; ++st)
+            sum += raw[g * (size_t)hipk::kCensusSlotWords + (size_t)st * hipk::kCensusStripeWords];
+        census_host_.push_back(sum);
+    }
+    census_dev_n_ = 0;
+}
+
+void HipEngine::census_discard() {
+    if (census_dev_n_ == 0) return;
+    synchronize();
+    HIP_CHECK(hipMemsetAsync(d_census_, 0, census_dev_n_ * kCensusSlotBytes, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    census_dev_n_ = 0;
+}
+
+void HipEngine::run_counted(u64 generations) {
     trace::Range range("gol.run");
     Armed armed(wd_.get());
     if (dual_ && !sub_current_) {
@@ -357,7 +421,7 @@ void HipEngine::finish_init() {
     if (!split_ && !dual_ && kern_[0] == "pipe")
         stats_.kernel = strprintf("pipe@%d(%dx%d,%d/CU)", pipe_k_, pipe_cur_.nw - 1, pipe_cur_.l, pipe_cur_.wg);
     if (rule_) {
-        const std::string rk = strprintf("rule@%d", kdepth_);
+        const std::string rk = strprintf(cfg_.census ? "census@%d" : "rule@%d", kdepth_);
         stats_.kernel = split_ ? rk + "+boundary:" + rk : rk;
     }
     if (res_) {
@@ -384,7 +448,7 @@ void HipEngine::finish_init() {
                 const PassKernel pk = pass_kernel(kind, ps[j]);
                 c += (j ? "+" : "") + (pk == PK_PIPE   ? strprintf("pipe@%d(%dx%d,%d/CU)", ps[j], g->nw - 1, g->l, g->wg)
                                        : pk == PK_TILE ? strprintf("tile@%d", ps[j])
-                                       : pk == PK_RULE ? strprintf("rule@%d", ps[j])
+                                       : pk == PK_RULE ? strprintf(cfg_.census ? "census@%d" : "rule@%d", ps[j])
                                                        : strprintf("temporal@%d", ps[j]));
             }
             tn += strprintf("%scut%d=%s", tn.empty() ? "" : " ", k, c.c_str());
@@ -441,6 +505,7 @@ void HipEngine::tile_superstep(int k) {
     const std::vector<int>& ps = pass_depths(k);
     first_pass(k, ps[0], ext_after(ps, 0), split_);
     cur_ ^= 1;
+    if (census_at_) census_at_ += (size_t)ps[0] * hipk::kCensusSlotWords;  // (the interior and the bands of a split pass add into the same slots)
     for (size_t j = 1; j < ps.size(); ++j) {
         // later passes need no halo: the ghost rows computed by the earlier passes carry the
         // neighbours' cells forward (communication-avoiding deep halos)
@@ -449,6 +514,7 @@ void HipEngine::tile_superstep(int k) {
         launch(0, ps[j], e, buf_[cur_], buf_[cur_ ^ 1], s_comp_);
         post(buf_[cur_ ^ 1], s_comp_, e);
         cur_ ^= 1;
+        if (census_at_) census_at_ += (size_t)ps[j] * hipk::kCensusSlotWords;
     }
     if (ps.size() > 1) mark_ready();  // the next exchange reads what the last pass wrote
 }
@@ -616,7 +682,11 @@ void HipEngine::launch(int kind, int k, i64 e, const u64* src, u64* dst, hipStre
             hipk::launch_step_pipe(g->nw, g->l, src, dst, p.d, p.waves, sp, s);
             pipe_used_ = true;
         } else if (pk == PK_RULE) {
-            if (dead_edges())
+            const hipk::BoardEdges edges{g_.row0, g_.dec.H, g_.word0(), g_.dec.W};
+            if (cfg_.census)
+                hipk::launch_step_census(k, cfg_.rule, dead_edges() ? &edges : nullptr, L_.w, src, dst, p.d, p.waves, sp,
+                                         census_at_, s);
+            else if (dead_edges())
                 hipk::launch_step_rule_bounded(k, cfg_.rule, {g_.row0, g_.dec.H, g_.word0(), g_.dec.W}, src, dst, p.d,
                                                p.waves, sp, s);
             else

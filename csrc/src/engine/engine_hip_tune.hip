@@ -173,7 +173,7 @@ void HipEngine::choose_schedule() {
         if (cfg_.sched == "auto" && split_used()) cands.push_back("split");
         // the one-tile superstep with its RCCL group captured in a graph (one replay per run)
         if (nbrs && device_transport_ && t_->graph_capturable() && cfg_.graph && !cfg_.profile && !cfg_.compat &&
-            cfg_.graph_rccl < 0)
+            cfg_.graph_rccl < 0 && !cfg_.census)  // (census runs are eager: graph_shape)
             cands.push_back("full+graph");
     }
     graph_rccl_on_ = cfg_.graph_rccl == 1;
@@ -377,6 +377,7 @@ void HipEngine::predict_run() {
     if (snap) {
         const int cur0 = cur_;
         const u64 gen0 = gen_;
+        census_mute_ = true;  // the samples run on the live board, which is restored: they are no part of the record
         HIP_CHECK(hipMemcpyAsync(snap, buf_[cur0], alloc_bytes_, hipMemcpyDeviceToDevice, s_comp_));
         synchronize();
         // warm-up (loads the sub-tile halves, as a warmup run does before a timed one), then the samples
@@ -400,6 +401,7 @@ void HipEngine::predict_run() {
         synchronize();
         HIP_CHECK(hipFree(snap));
         gen_ = gen0;
+        census_mute_ = false;
         sub_current_ = false;  // the halves hold a later generation: reload them from the board at the next run
         canon_stale_ = false;
     } else if (res_) {
@@ -439,7 +441,7 @@ void HipEngine::time_schedule(const std::string& c, int k, int reps, bool eager)
     // candidate): `reps` supersteps captured once per candidate (round 0's warm-up call,
     // after one eager superstep that loads every kernel variant), one replay per call.
     const bool graphed = !eager && (c == "full+graph" ||
-                                    (c == "local" && cfg_.graph && !cfg_.profile && !cfg_.compat && graph_ok_));
+                                    (c == "local" && cfg_.graph && !cfg_.profile && !cfg_.compat && graph_ok_ && !cfg_.census));
     if (graphed) {
         const std::string base = c == "local" ? "local" : "full";
         SchedGraph& sg = sched_graphs_[c];

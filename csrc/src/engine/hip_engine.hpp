@@ -158,6 +158,7 @@ class HipEngine : public Engine {
     }
 
     void run(u64 generations) override;
+    void run_counted(u64 generations);  // run() proper (census mode: one chunk of the call)
 
     void device_barrier() override;
     std::map<std::string, double> phase_probe(int k) override;
@@ -301,9 +302,17 @@ class HipEngine : public Engine {
         return e;
     }
     // The streaming kernel of this engine: step_rule under a rule (rule_), else step_temporal.
-    bool depth_ok(int k) const { return rule_ ? hipk::rule_depth_supported(k) : hipk::step_depth_supported(k); }
-    int max_depth() const { return rule_ ? hipk::max_rule_depth() : hipk::max_step_depth(); }
+    // (in census mode step_census, at its own depths, on either boundary)
+    bool depth_ok(int k) const {
+        if (cfg_.census) return k >= 1 && k <= hipk::max_census_depth();
+        return rule_ ? hipk::rule_depth_supported(k) : hipk::step_depth_supported(k);
+    }
+    int max_depth() const {
+        if (cfg_.census) return hipk::max_census_depth();
+        return rule_ ? hipk::max_rule_depth() : hipk::max_step_depth();
+    }
     int blocks_per_cu(int k, u32 flags) const {
+        if (cfg_.census) return hipk::census_blocks_per_cu(k, flags, dead_edges());
         if (dead_edges()) return hipk::rule_bounded_blocks_per_cu(k, flags);
         return rule_ ? hipk::rule_blocks_per_cu(k, flags) : hipk::step_blocks_per_cu(k, flags);
     }
@@ -710,6 +719,25 @@ class HipEngine : public Engine {
     std::map<int, std::vector<HaloItem>> items_;
     std::map<i64, hipGraphExec_t> graphs_;
     std::vector<u64*> dstage_s_, dstage_r_, hstage_s_, hstage_r_;
+    // ----- census (EngineConfig::census) -----
+    // The kernels of run() add this rank's counts into d_census_ (slots of kCensusSlotWords words, each the
+    // partial sums census_collect() adds up): slot census_dev_n_ + i is generation i + 1 of
+    // the run() call in progress, census_at_ the slot of the next pass's first generation (advanced by
+    // tile_superstep; null outside run(), so every init-time timing launch counts nothing).  Slots past
+    // census_dev_n_ are always zero: the buffer is zeroed when it is allocated and its used part again when
+    // census_collect() has copied it to the host (both synchronise; run() never does), so a pass's launches on
+    // either stream find zeroed slots whatever the streams' order.  census_mute_: run() calls that are timing
+    // samples on the live board (predict_run restores board and generation afterwards) record nothing.
+    void census_collect() override;
+    void census_discard() override;
+    void census_begin(u64 generations);  // run(): room for the call's counts (grows the buffer: rare, synchronises)
+    u64* d_census_ = nullptr;
+    size_t census_cap_ = 0, census_dev_n_ = 0;
+    u64* census_at_ = nullptr;
+    bool census_mute_ = false;
+    // Most slots the device buffer holds before run() moves them to the host (32 MiB: a slot is 16 lines, 2 KiB)
+    static constexpr size_t kCensusMaxSlots = (size_t)1 << 14;
+    static constexpr size_t kCensusSlotBytes = (size_t)hipk::kCensusSlotWords * sizeof(u64);
     bool res_ = false;  // supersteps run the resident kernel
     int res_kin_ = 0;   // its generations per in-kernel halo exchange
     std::map<int, ResPlan> res_plans_;

@@ -168,6 +168,7 @@ EngineConfig engine_config(const Options& o, const std::string& backend, int dev
     c.kernel = env_str("GOL_KERNEL", "auto");
     c.rule = Rule::parse(o.rule.empty() ? env_str("GOL_RULE", "B3/S23") : o.rule);
     c.boundary = parse_boundary(o.boundary.empty() ? env_str("GOL_BOUNDARY", "torus") : o.boundary);
+    c.census = o.census;
     c.tile_waves = (int)env_int("GOL_TILE_WAVES", 8);
     c.tune_tile_waves = getenv("GOL_TILE_WAVES") == nullptr;
     c.transport = (o.transport == "rccl" || o.transport == "p2p") ? "device" : o.transport;
@@ -401,6 +402,7 @@ u64 load_checkpoint(Engine& eng, const std::string& prefix) {
         }
         close(fd);
         eng.set_tile_words(words);
+        eng.census_restart(hd.generation);  // (census mode: an empty record that starts at the snapshot's generation)
     } catch (...) {
         close(fd);
         throw;
@@ -445,6 +447,7 @@ void write_metrics(const Options& o, Engine& eng, const CliArgs& a, double durat
     f << "  \"kernel\": \"" << s.kernel << "\",\n";
     f << "  \"rule\": \"" << s.rule << "\",\n";
     f << "  \"boundary\": \"" << s.boundary << "\",\n";
+    f << "  \"census\": " << (s.census ? "true" : "false") << ",\n";
     f << "  \"schedule\": \"" << s.schedule << "\",\n";
     f << "  \"autotune\": \"" << s.tuning << "\",\n";
     f << "  \"plan_waves\": " << s.plan_waves << ",\n  \"lane_efficiency\": " << s.lane_efficiency << ",\n";
@@ -574,6 +577,23 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
             write_dumps(*eng, fp);
             fclose(fp);
             fp = nullptr;
+        }
+        if (!o.census_out.empty()) {
+            // the run's series (collective); rank 0 writes it, and every rank learns whether that worked
+            const std::pair<u64, std::vector<u64>> cs = eng->census();
+            u64 ok = 1;
+            if (rank == 0) {
+                FILE* cf = fopen(o.census_out.c_str(), "w");
+                ok = cf != nullptr;
+                if (cf) {
+                    ok = fputs("generation,population\n", cf) >= 0;
+                    for (size_t i = 0; i < cs.second.size() && ok; ++i)
+                        ok = fprintf(cf, "%llu,%llu\n", (unsigned long long)(cs.first + 1 + i), (unsigned long long)cs.second[i]) > 0;
+                    ok = (fclose(cf) == 0) && ok;
+                }
+            }
+            t->broadcast(&ok, sizeof(ok), 0);
+            if (!ok) throw Error("GOL_CENSUS_OUT: cannot write " + o.census_out);
         }
         if (!o.rle_out.empty()) {
             RlePattern out;

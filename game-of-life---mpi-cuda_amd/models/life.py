@@ -64,6 +64,11 @@ class Simulation:
                   ``step_rule_bounded`` for every rule, B3/S23 included (generic-kernel speed); without
                   ``compat``, ``subtiles=2`` or the torus-only kernels.  Windows and stamps must lie inside
                   a bounded board.
+    census:       census mode (default off; GOL_CENSUS): every generation :meth:`step` computes also yields the
+                  global population of that generation, read with :meth:`census`.  HIP: the census kernel
+                  ``step_census`` counts inside every pass, for every rule and either boundary (generic-kernel
+                  speed, passes of at most ``max_census_depth`` generations, eager launches); without
+                  ``compat``, ``subtiles=2`` or the specialised kernels.
     compat:       reproduce the reference's halo quirks (frozen gen-0 halos, P<=2 swap).
     watchdog:     seconds without progress before the job is aborted (0 = off; GOL_WATCHDOG).
     """
@@ -99,6 +104,7 @@ class Simulation:
         subtile_overlap: Optional[int] = None,
         rule: str = os.environ.get("GOL_RULE", "B3/S23"),
         boundary: Optional[str] = None,
+        census: Optional[bool] = None,
     ):
         self.transport = transport if transport is not None else _gol.SelfTransport()
         P, rank = self.transport.size(), self.transport.rank()
@@ -131,6 +137,21 @@ class Simulation:
                 raise ValueError("subtiles=2 implements the torus only, not boundary dead")
             if self.backend == "hip" and kernel in ("temporal", "tile", "pipe", "resident", "lds"):
                 raise ValueError(f"kernel {kernel!r} implements the torus only, not boundary dead")
+        if census is None:  # (read per call, as the boundary is)
+            census = os.environ.get("GOL_CENSUS", "0").lower() in ("1", "true", "yes", "on")
+        cfg.census = bool(census)
+        if cfg.census:
+            if compat:
+                raise ValueError("census=True with compat=True: compat mode runs the reference's loop, not the census kernel")
+            if int(subtiles) == 2:
+                raise ValueError("census=True with subtiles=2: the sub-tile halves do not run the census kernel")
+            if self.backend == "hip" and kernel in ("temporal", "tile", "pipe", "resident", "lds"):
+                raise ValueError(f"kernel {kernel!r} counts no census: the census kernel runs every pass (use auto or rule)")
+            if self.backend == "hip" and int(kernel_depth) > _gol.max_census_depth():
+                raise ValueError(
+                    f"census=True: kernel_depth {kernel_depth} exceeds the census kernel's deepest pass, "
+                    f"{_gol.max_census_depth()} generations"
+                )
         cfg.subtiles = int(subtiles)  # 2 / 0 / -1 auto: two sub-tiles per rank on two streams (HIP, 1-D)
         cfg.run_hint = int(run_hint)  # generations of the runs to come: one replay graph covers them
         cfg.rows_per_wave = rows_per_wave
@@ -198,6 +219,22 @@ class Simulation:
     def population(self) -> int:
         """Global live-cell count (collective)."""
         return int(self.engine.population())
+
+    def census(self):
+        """``(start, counts)``: ``counts[i]`` is the global population at generation ``start + 1 + i``, a uint64 array
+        with one entry per generation computed since the record was cleared (by :meth:`init`, :meth:`load_rle`,
+        :meth:`restore` or :meth:`census_clear`).  Collective; every rank gets the same array.  Needs
+        ``census=True``."""
+        if not self.config.census:
+            raise ValueError("census() needs a simulation built with census=True (or GOL_CENSUS=1)")
+        start, counts = self.engine.census()
+        return int(start), counts
+
+    def census_clear(self) -> None:
+        """Forget the recorded series; the next one starts at the generation reached."""
+        if not self.config.census:
+            raise ValueError("census_clear() needs a simulation built with census=True (or GOL_CENSUS=1)")
+        self.engine.census_clear()
 
     def fingerprint(self) -> int:
         """Decomposition-invariant fingerprint of the global board (collective)."""

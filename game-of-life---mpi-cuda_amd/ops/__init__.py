@@ -3,6 +3,7 @@ native kernels through the ``_gol`` extension."""
 from .bitpack import pack_cells, unpack_words  # noqa: F401
 from .oracle import (  # noqa: F401
     initial_board,
+    numpy_census,
     numpy_step,
     numpy_step_rule,
     numpy_step_rule_bounded,

@@ -129,6 +129,20 @@ def numpy_step_rule_bounded(board: np.ndarray, rule, generations: int = 1) -> np
     return b
 
 
+def numpy_census(board: np.ndarray, rule, gens: int, bounded: bool = False, return_board: bool = False):
+    """The populations after generations ``1 .. gens`` of ``board`` under ``rule`` as a uint64 array (the oracle of
+    the engines' census mode), on the torus or, ``bounded``, on a board with dead edges.  One generation of
+    :func:`numpy_step_rule` / :func:`numpy_step_rule_bounded` at a time; ``return_board`` also returns the last
+    board."""
+    step = numpy_step_rule_bounded if bounded else numpy_step_rule
+    b = np.asarray(board, dtype=np.uint8)
+    counts = np.zeros(int(gens), dtype=np.uint64)
+    for g in range(int(gens)):
+        b = step(b, rule, 1)
+        counts[g] = int(b.sum(dtype=np.uint64))
+    return (counts, b) if return_board else counts
+
+
 def torch_step_rule(board, rule, generations: int = 1, device=None):
     """A life-like rule on a torus with torch conv2d (fp32, exact for counts <= 8).  Returns a torch uint8 tensor."""
     import torch
