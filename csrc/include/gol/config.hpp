@@ -55,6 +55,8 @@ struct Options {
     std::string pattern_at = "";    // GOL_PATTERN_AT  row,col of the file's first cell (default: centred)
     bool census = false;            // GOL_CENSUS    census mode: the population of every generation of the run
     std::string census_out = "";    // GOL_CENSUS_OUT  implies it; rank 0 writes "generation,population" lines there
+    bool signature = false;         // GOL_SIGNATURE signature mode: the board signature and population of every generation
+    std::string signature_out = ""; // GOL_SIGNATURE_OUT  implies it; rank 0 writes "generation,population,signature" lines
     std::string rle_out = "";       // GOL_RLE_OUT   rank 0 writes the final global board as RLE (<= 2^26 cells)
     std::string rule = "";          // the run's rule when GOL_PATTERN_FILE names one and GOL_RULE is unset
     std::string boundary = "";      // the run's boundary when GOL_PATTERN_FILE names a topology and GOL_BOUNDARY is

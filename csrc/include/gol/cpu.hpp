@@ -45,8 +45,11 @@ void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, co
 // torus machinery delivered across the board's edges), then every generation's output.
 // counts (census; k slots, or null): counts[g] += the live cells of the tile itself after generation g + 1: rows
 // [0, h), words [0, nw) under the storage mask, no ghost row or word.
+// sigs (signature mode; k slots, or null): sigs[g] += the tile's share of the board signature (gol/signature.hpp)
+// after generation g + 1, over the same cells, keyed by edges.row0 and edges.word0 (the tile's place; needed on the
+// torus too).
 u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule = Rule(), const Edges& edges = Edges(),
-               u64* counts = nullptr);
+               u64* counts = nullptr, u64* sigs = nullptr);
 
 // x-periodic ghost words (and tail ghost bits) for rows [r_lo, r_hi).
 void fill_ghost_cols_wrap(u64* buf, const Layout& L, i64 r_lo, i64 r_hi);
@@ -63,6 +66,8 @@ void insert_words(u64* buf, const Layout& L, const u64* dense);
 // Live-cell count and decomposition-invariant fingerprint of the tile.
 u64 population(const u64* buf, const Layout& L);
 u64 fingerprint(const u64* buf, const Layout& L, i64 grow0, i64 gword0, i64 gwords);
+// The tile's share of the board signature (gol/signature.hpp): rows [0, h), words [0, nw) under the storage mask.
+u64 signature(const u64* buf, const Layout& L, i64 grow0, i64 gword0);
 
 }  // namespace cpu
 }  // namespace gol

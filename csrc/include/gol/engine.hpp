@@ -61,6 +61,10 @@ struct EngineConfig {
     bool census = false;              // census mode (GOL_CENSUS): every generation run() computes also yields the
                                       // global live-cell count of that generation (Engine::census).  HIP: the
                                       // census kernel step_census runs every pass, for every rule and boundary
+    bool signature = false;           // signature mode (GOL_SIGNATURE): every generation run() computes also yields
+                                      // the board signature (gol/signature.hpp) and the population of that
+                                      // generation (Engine::signatures).  HIP: step_signature runs every pass.
+                                      // Not together with census (signature mode records the population too)
     int tile_waves = 8;               // tile kernel: waves per workgroup (4, 8, 16)
     bool tune_tile_waves = true;      // GOL_KERNEL=auto may also try 8 waves (false: GOL_TILE_WAVES set)
     std::string transport = "auto";   // auto | device | host  (host = stage halos through host memory)
@@ -110,6 +114,7 @@ struct EngineStats {
     std::string rule;          // the rule, canonical (B3/S23)
     std::string boundary;      // torus | dead
     bool census = false;       // census mode
+    bool signature = false;    // signature mode
     std::string schedule;      // superstep schedule: local (no neighbours) | split | full
     std::string tuning;        // init-time measurements behind the auto choices (HIP)
     bool registered = false;   // HIP + RCCL: the boards are registered with the communicator (zero-copy halos)
@@ -150,7 +155,27 @@ class Engine {
     // engine that is not in census mode.
     std::pair<u64, std::vector<u64>> census();
     void census_clear();
-    void census_restart(u64 generation);  // an empty record that starts at `generation` (load_checkpoint)
+    void census_restart(u64 generation);  // an empty record that starts at `generation` (load_checkpoint; both modes)
+
+    // ----- signatures (EngineConfig::signature) -----
+    // The board signature (gol/signature.hpp): a linear, position-keyed 64-bit hash of the global board, equal for
+    // every decomposition.  signatures() is census() of signature mode: (start, signatures, populations), entry i
+    // for generation start + 1 + i, with the same start / clear / restart rules (census_restart serves both modes)
+    // and the same collective sum over the ranks (wrapping, for the signatures).
+    struct SignatureSeries {
+        u64 start = 0;
+        std::vector<u64> signatures, populations;
+    };
+    SignatureSeries signatures();
+    void signatures_clear();
+    // Collective, any mode: the signature of the current board.
+    u64 signature();
+    // snapshot(): keep a copy of this rank's current board (a third tile-sized buffer, allocated on first use; throws
+    // when the memory is not there).  snapshot_diff(): collective, the number of cells of the GLOBAL board that
+    // differ between the current board and the snapshot; throws, before any communication, without a snapshot.
+    void snapshot();
+    u64 snapshot_diff();
+    bool recording() const { return cfg_.census || cfg_.signature; }  // run() keeps a per-generation record
 
     // ----- views and pattern stamping -----
     // Global board coordinates on the torus: a window or a pattern may start anywhere (r0, c0 are taken
@@ -285,10 +310,17 @@ class Engine {
 
     // Census record of this rank: the counts already on the host; a backend that keeps counts elsewhere (HIP: a
     // device buffer the kernels add into) appends them in census_collect() and drops them in census_discard().
+    // (signature mode: census_host_ holds the populations, sig_host_ the signatures, of the same generations)
     virtual void census_collect() {}
     virtual void census_discard() {}
-    std::vector<u64> census_host_;
+    std::vector<u64> census_host_, sig_host_;
     u64 census_start_ = 0;
+    void sum_series(std::vector<u64>& series, const char* what);  // collective: the ranks' series added up (wrapping)
+    // This rank's part of signature(), snapshot() and snapshot_diff().
+    virtual u64 local_signature() = 0;
+    virtual void snapshot_local() = 0;
+    virtual u64 snapshot_diff_local() = 0;
+    bool have_snapshot_ = false;
 
     Geometry g_;
     EngineConfig cfg_;

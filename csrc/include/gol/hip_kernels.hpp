@@ -11,6 +11,9 @@
 //                       every level masked to the board's cells (rule_bounded_kernel.hip; K = 1..8).
 //   step_census<K>    — step_rule / step_rule_bounded that also counts the tile's live cells after every generation
 //                       of the pass: a masked v_bcnt per level, K atomics per wave (census_kernel.hip; K = 1..8).
+//   step_signature<K> — step_census that also hashes the tile after every generation of the pass: the linear,
+//                       position-keyed board signature, two multiplies and two 64-bit multiply-adds per word and
+//                       level (signature_kernel.hip; K = 1..8; with k_signature and k_board_diff).
 //   step_lds          — single-generation LDS-tiled variant (tile + ghost words staged in LDS);
 //                       kept as a measured alternative (GOL_KERNEL=lds).
 //   fill_ghost_cols   — x-periodic ghost words for widths that are not a multiple of 64.
@@ -111,6 +114,24 @@ int max_census_depth();
 int census_blocks_per_cu(int k, u32 flags, bool bounded);
 void launch_step_census(int k, const Rule& rule, const BoardEdges* edges, i64 tile_cols, const u64* src, u64* dst,
                         const LaneDesc* plan, i64 n_waves, const StepParams& p, u64* counts, hipStream_t s);
+// step_signature<K> (signature_kernel.hip): step_census that also adds each generation's share of the board
+// signature (gol/signature.hpp).  `place` is the tile's place on the board (always needed: the keys are global
+// coordinates); `bounded` selects the dead-edge variant.  Generation g + 1 of the pass's k goes to the slot at
+// slots + g * kSigSlotWords: kSigStripes partial counts kSigStripeWords words apart, then, kSigSigOffset words on,
+// as many partial signatures (a 128-byte line each; the host adds them up, wrapping).  nullptr: record nothing.
+// Plans, StepParams, rows and words read and written, and the argument checks, as launch_step_census.
+// Depths 1 .. max_signature_depth().
+constexpr int kSigStripes = 16, kSigStripeWords = 16;
+constexpr int kSigSigOffset = kSigStripes * kSigStripeWords;  // u64 words from a slot's counts to its signatures
+constexpr int kSigSlotWords = 2 * kSigSigOffset;              // u64 words from one generation's slot to the next
+int max_signature_depth();
+int signature_blocks_per_cu(int k, u32 flags, bool bounded);
+void launch_step_signature(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src,
+                           u64* dst, const LaneDesc* plan, i64 n_waves, const StepParams& p, u64* slots, hipStream_t s);
+// out[0] += the signature of the tile in `buf` at (grow0, gword0) (wrapping; out zeroed by the caller).
+void launch_signature(const u64* buf, const Layout& L, i64 grow0, i64 gword0, u64* out, hipStream_t s);
+// out[0] += the number of cells of the tile that differ between boards a and b (one layout; out zeroed by the caller).
+void launch_board_diff(const u64* a, const u64* b, const Layout& L, u64* out, hipStream_t s);
 // LDS-resident temporal kernel (step_tile): one workgroup of `nw_per_wg` (4, 8, 16) waves per plan
 // wave; `rows` = the plan's rows per chunk (<= tile_max_rows(k), the 160 KiB LDS limit).
 constexpr size_t kMaxLdsBytes = 160 * 1024;

@@ -110,6 +110,7 @@ py::dict stats_dict(const EngineStats& s) {
     d["rule"] = s.rule;
     d["boundary"] = s.boundary;
     d["census"] = s.census;
+    d["signature"] = s.signature;
     d["schedule"] = s.schedule;
     d["kernel_depth"] = s.kernel_depth;
     d["tile_waves"] = s.tile_waves;
@@ -274,6 +275,7 @@ PYBIND11_MODULE(_gol, m) {
         .def_readwrite("graph_rccl", &EngineConfig::graph_rccl)
         .def_readwrite("plan_xcds", &EngineConfig::plan_xcds)
         .def_readwrite("census", &EngineConfig::census)
+        .def_readwrite("signature", &EngineConfig::signature)
         // the life-like rule as a string (any form Rule::parse takes; reads back canonical, B3/S23)
         .def_property(
             "rule", [](const EngineConfig& c) { return c.rule.str(); },
@@ -347,6 +349,24 @@ PYBIND11_MODULE(_gol, m) {
                  return py::make_tuple(c.first, a);
              })
         .def("census_clear", &Engine::census_clear, py::call_guard<py::gil_scoped_release>())
+        // signature mode (collective): (start, signatures, populations), entry i for generation start + 1 + i
+        .def("signatures",
+             [](Engine& e) {
+                 Engine::SignatureSeries s;
+                 {
+                     py::gil_scoped_release r;
+                     s = e.signatures();
+                 }
+                 py::array_t<u64> a((py::ssize_t)s.signatures.size()), b((py::ssize_t)s.populations.size());
+                 if (!s.signatures.empty()) std::memcpy(a.mutable_data(), s.signatures.data(), s.signatures.size() * sizeof(u64));
+                 if (!s.populations.empty()) std::memcpy(b.mutable_data(), s.populations.data(), s.populations.size() * sizeof(u64));
+                 return py::make_tuple(s.start, a, b);
+             })
+        .def("signatures_clear", &Engine::signatures_clear, py::call_guard<py::gil_scoped_release>())
+        // any mode (collective): the signature of the current board; a copy of the board, and the cells that differ from it
+        .def("signature", &Engine::signature, py::call_guard<py::gil_scoped_release>())
+        .def("snapshot", &Engine::snapshot, py::call_guard<py::gil_scoped_release>())
+        .def("snapshot_diff", &Engine::snapshot_diff, py::call_guard<py::gil_scoped_release>())
         // views and stamping (collective; global board coordinates on the torus)
         .def(
             "window",
@@ -509,6 +529,7 @@ PYBIND11_MODULE(_gol, m) {
     m.def("hip_device_count", []() { return hip_device_count(nullptr); });
     m.def("hip_set_device", &hip_set_device);
     m.def("max_census_depth", []() { return hipk::max_census_depth(); });  // deepest pass of the census kernel
+    m.def("max_signature_depth", []() { return hipk::max_signature_depth(); });  // ... of the signature kernel
     m.def(
         "naive_byte_run",
         [](i64 N, int gens, int threads, bool sync_each, u64 seed) {

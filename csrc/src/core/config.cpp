@@ -89,6 +89,8 @@ Options options_from_env() {
     o.rle_out = env_str("GOL_RLE_OUT", "");
     o.census_out = env_str("GOL_CENSUS_OUT", "");
     o.census = env_flag("GOL_CENSUS", false) || !o.census_out.empty();
+    o.signature_out = env_str("GOL_SIGNATURE_OUT", "");
+    o.signature = env_flag("GOL_SIGNATURE", false) || !o.signature_out.empty();
     if (o.halo_depth < 0 || o.halo_depth > 128) throw Error("GOL_HALO_DEPTH must be in 1..128 (0 = auto)");
     if (o.kernel_depth < 0 || o.kernel_depth > 64) throw Error("GOL_KERNEL_DEPTH must be in 1..64 (0 = auto)");
     return o;

@@ -4,6 +4,7 @@
 
 #include "gol/bits.hpp"
 #include "gol/cpu.hpp"
+#include "gol/signature.hpp"
 
 namespace gol {
 namespace cpu {
@@ -113,7 +114,7 @@ void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, co
     }
 }
 
-u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges, u64* counts) {
+u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges, u64* counts, u64* sigs) {
     if (k < 1 || k > L.R) throw Error(strprintf("superstep depth %d outside 1..%d", k, L.R));
     u64* src = a;
     u64* dst = b;
@@ -122,6 +123,7 @@ u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const E
         i64 ext = k - 1 - g;
         step_rows(src, dst, L, -ext, L.h + ext, rule, edges);
         if (counts) counts[g] += population(dst, L);  // the tile's own cells: rows [0, h), words [0, nw), no ghosts
+        if (sigs) sigs[g] += signature(dst, L, edges.row0, edges.word0);
         std::swap(src, dst);
     }
     return src;
@@ -192,6 +194,15 @@ u64 fingerprint(const u64* buf, const Layout& L, i64 grow0, i64 gword0, i64 gwor
         const u64* row = buf + L.index(r, 0);
         for (i64 c = 0; c < L.nw; ++c)
             s += fingerprint_word((u64)(grow0 + r) * (u64)gwords + (u64)(gword0 + c), merge_word(row[c]) & L.mask(c));
+    }
+    return s;
+}
+
+u64 signature(const u64* buf, const Layout& L, i64 grow0, i64 gword0) {
+    u64 s = 0;
+    for (i64 r = 0; r < L.h; ++r) {
+        const u64* row = buf + L.index(r, 0);
+        for (i64 c = 0; c < L.nw; ++c) s += signature_word(grow0 + r, gword0 + c, row[c] & storage_mask(c, L.w));
     }
     return s;
 }

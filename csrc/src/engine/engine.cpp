@@ -51,6 +51,15 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
                 if (cfg_.kernel == k)
                     throw Error("kernel '" + cfg_.kernel + "' counts no census: the census kernel runs every pass (use kernel auto or rule)");
     }
+    if (cfg_.signature) {
+        if (cfg_.census) throw Error("signature together with census: signature mode already records the population of every generation");
+        if (cfg_.compat) throw Error("signature with GOL_COMPAT=reference: compat mode runs the reference's loop, not the signature kernel");
+        if (cfg_.subtiles == 2) throw Error("two sub-tiles per rank (GOL_SUBTILES=2) do not run the signature kernel");
+        if (cfg_.backend == "hip")
+            for (const char* k : {"temporal", "tile", "pipe", "resident", "lds"})
+                if (cfg_.kernel == k)
+                    throw Error("kernel '" + cfg_.kernel + "' records no signatures: the signature kernel runs every pass (use kernel auto or rule)");
+    }
     if (t_->size() != g_.dec.P || t_->rank() != g_.rank)
         throw Error(strprintf("transport (rank %d of %d) does not match the geometry (rank %d of %d)", t_->rank(),
                               t_->size(), g_.rank, g_.dec.P));
@@ -78,7 +87,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     const bool sub_tall = cfg_.backend == "hip" && (cfg_.subtiles == 2 || cfg_.subtiles < 0) && !two_d() && strip_rows >= kSubtileMinRows &&
                           g_.dec.W % 64 == 0 && !cfg_.force_split && !cfg_.profile && !cfg_.compat &&
                           cfg_.kernel != "lds" && cfg_.kernel != "tile" && cfg_.kernel != "pipe" &&
-                          cfg_.kernel != "rule" && cfg_.rule.is_conway() && !dead_edges() && !cfg_.census;
+                          cfg_.kernel != "rule" && cfg_.rule.is_conway() && !dead_edges() && !recording();
     // (1-D strips with neighbours: 128 measured 1-3% faster than 64 through RCCL self-exchange,
     // 4096 x 32768 2.44 -> 2.36, 8192 x 65536 5.93 -> 5.85 us/gen; profiles/per_rank_tiles_self_exchange.txt)
     const int want = cfg_.halo_depth > 0 ? cfg_.halo_depth : (sub_tall || tall_strips ? 128 : (tall_tiles ? 56 : 32));
@@ -93,6 +102,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     stats_.rule = cfg_.rule.str();
     stats_.boundary = boundary_name(cfg_.boundary);
     stats_.census = cfg_.census;
+    stats_.signature = cfg_.signature;
     std::string f = env_str("GOL_FAULT", "");
     if (!f.empty()) {
         int fr = -1;
@@ -194,15 +204,22 @@ void Engine::init(const PatternSpec& p) {
     stats_.rule = cfg_.rule.str();
     stats_.boundary = boundary_name(cfg_.boundary);
     stats_.census = cfg_.census;
+    stats_.signature = cfg_.signature;
     census_restart(0);
+    have_snapshot_ = false;
     if (t_->size() > 1) {
         // every rank must run the same rule on the same boundary, in the same census mode: agreed like the schedule,
         // by reductions every rank sees (so on a mismatch every rank raises and none waits for a peer).  One code:
         // the rule's 32 bits, the boundary above them, the census mode above that (exact in a double).
-        const double code = (double)cfg_.rule.code() + (double)((u64)cfg_.boundary << 32) + (double)((u64)cfg_.census << 40);
+        // (signature mode one bit above the census mode's)
+        const double code = (double)cfg_.rule.code() + (double)((u64)cfg_.boundary << 32) + (double)((u64)cfg_.census << 40) +
+                            (double)((u64)cfg_.signature << 41);
         const double lo = t_->allreduce_min(code), hi = t_->allreduce_max(code);
         if (lo != hi) {
             const u64 clo = (u64)lo, chi = (u64)hi;
+            if ((clo >> 41) != (chi >> 41))
+                throw Error(strprintf("the ranks disagree on the signature mode: rank %d has signature %s (some ranks on, some off)",
+                                      g_.rank, cfg_.signature ? "on" : "off"));
             if ((clo >> 40) != (chi >> 40))
                 throw Error(strprintf("the ranks disagree on the census mode: rank %d has census %s (some ranks on, some off)",
                                       g_.rank, cfg_.census ? "on" : "off"));
@@ -332,7 +349,66 @@ void Engine::census_clear() {
 void Engine::census_restart(u64 generation) {
     census_discard();
     census_host_.clear();
+    sig_host_.clear();
     census_start_ = generation;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Signatures (signature mode's record: census_host_ the populations, sig_host_ the signatures)
+// ---------------------------------------------------------------------------------------------
+
+void Engine::sum_series(std::vector<u64>& out, const char* what) {
+    if (t_->size() == 1) return;
+    const size_t n = out.size();
+    std::vector<std::vector<u8>> all;
+    t_->gatherv(out.data(), n * sizeof(u64), &all, 0);
+    u64 ok = 1;
+    if (g_.rank == 0)
+        for (int q = 1; q < t_->size(); ++q) {
+            if (all[(size_t)q].size() != n * sizeof(u64)) {
+                ok = 0;
+                break;
+            }
+            u64 part = 0;
+            for (size_t i = 0; i < n; ++i) {
+                memcpy(&part, all[(size_t)q].data() + i * sizeof(u64), sizeof(u64));
+                out[i] += part;
+            }
+        }
+    t_->broadcast(&ok, sizeof(ok), 0);
+    if (!ok) throw Error(std::string(what) + ": the ranks' series differ in length (every rank must run the same generations)");
+    if (n > 0) t_->broadcast(out.data(), n * sizeof(u64), 0);
+}
+
+Engine::SignatureSeries Engine::signatures() {
+    if (!cfg_.signature)
+        throw Error("signatures(): this engine is not in signature mode (EngineConfig::signature, Simulation(signature=True), GOL_SIGNATURE=1)");
+    census_collect();
+    SignatureSeries s;
+    s.start = census_start_;
+    s.signatures = sig_host_;
+    s.populations = census_host_;
+    sum_series(s.signatures, "signatures");
+    sum_series(s.populations, "signatures");
+    return s;
+}
+
+void Engine::signatures_clear() {
+    if (!cfg_.signature) throw Error("signatures_clear(): this engine is not in signature mode");
+    census_collect();
+    census_restart(census_start_ + (u64)census_host_.size());
+}
+
+u64 Engine::signature() { return t_->allreduce_sum(local_signature()); }
+
+void Engine::snapshot() {
+    snapshot_local();
+    have_snapshot_ = true;
+}
+
+u64 Engine::snapshot_diff() {
+    if (!have_snapshot_) throw Error("snapshot_diff(): no snapshot has been taken since init (call snapshot() first)");
+    return t_->allreduce_sum(snapshot_diff_local());
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -507,6 +583,16 @@ class CpuEngine : public Engine {
         return {cpu::population(cur_, L_),
                 cpu::fingerprint(cur_, L_, g_.row0, g_.word0(), g_.global_words())};
     }
+    u64 local_signature() override { return cpu::signature(cur_, L_, g_.row0, g_.word0()); }
+    void snapshot_local() override { snap_.assign(cur_, cur_ + L_.words()); }
+    u64 snapshot_diff_local() override {
+        u64 n = 0;
+        for (i64 r = 0; r < L_.h; ++r) {
+            const u64 *a = cur_ + L_.index(r, 0), *b = snap_.data() + L_.index(r, 0);
+            for (i64 c = 0; c < L_.nw; ++c) n += (u64)__builtin_popcountll((a[c] ^ b[c]) & storage_mask(c, L_.w));
+        }
+        return n;
+    }
 
     void read_window_local(i64 r0, i64 c0, i64 rows, i64 cols, u8* out, i64 stride) override {
         check_window(r0, c0, rows, cols);
@@ -594,12 +680,17 @@ class CpuEngine : public Engine {
             exchange(k);
             if (self_y()) cpu::fill_ghost_rows_wrap(cur_, L_);
         }
-        u64* counts = nullptr;
-        if (cfg_.census) {  // this rank's own cells after each of the k generations
+        u64 *counts = nullptr, *sigs = nullptr;
+        if (recording()) {  // this rank's own cells after each of the k generations
             census_host_.resize(census_host_.size() + (size_t)k, 0);
             counts = census_host_.data() + (census_host_.size() - (size_t)k);
         }
-        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, cpu::Edges(cfg_.boundary, g_), counts);
+        if (cfg_.signature) {
+            sig_host_.resize(sig_host_.size() + (size_t)k, 0);
+            sigs = sig_host_.data() + (sig_host_.size() - (size_t)k);
+        }
+        cpu::Edges place(cfg_.boundary, g_);  // (the signature's keys need the tile's place on the torus too)
+        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, place, counts, sigs);
         if (res != cur_) std::swap(cur_, oth_);
         if (self_x()) cpu::fill_ghost_cols_wrap(cur_, L_, 0, L_.h);
     }
@@ -620,7 +711,7 @@ class CpuEngine : public Engine {
     }
 
    private:
-    std::vector<u64> a_, b_;
+    std::vector<u64> a_, b_, snap_;
     u64* cur_;
     u64* oth_;
     std::vector<std::vector<u64>> stage_s_, stage_r_;

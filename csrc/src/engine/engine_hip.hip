@@ -42,7 +42,11 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
     // in every pass of every plan kind.  (Engine::Engine refused the specialised kernels with such a rule.)
     // A bounded board runs step_rule_bounded, for every rule including B3/S23 (there is no bounded step_temporal).
     // Census mode runs step_census, likewise for every rule and either boundary.
-    rule_ = kernel_ == "rule" || !cfg_.rule.is_conway() || dead_edges() || cfg_.census;
+    // Signature mode runs step_signature in the same way.
+    rule_ = kernel_ == "rule" || !cfg_.rule.is_conway() || dead_edges() || recording();
+    if (cfg_.signature && cfg_.kernel_depth > hipk::max_signature_depth())
+        throw Error(strprintf("signature: kernel_depth %d exceeds the signature kernel's deepest pass, %d generations (GOL_KERNEL_DEPTH)",
+                              cfg_.kernel_depth, hipk::max_signature_depth()));
     if (cfg_.census && cfg_.kernel_depth > hipk::max_census_depth())
         throw Error(strprintf("census: kernel_depth %d exceeds the census kernel's deepest pass, %d generations (GOL_KERNEL_DEPTH)",
                               cfg_.kernel_depth, hipk::max_census_depth()));
@@ -223,7 +227,7 @@ HipEngine::~HipEngine() {
     for (void* q : {(void*)res_status_, (void*)res_scratch_[0], (void*)res_scratch_[1]})
         if (q) hipFree(q);
     for (void* p : deferred_free_) hipFree(p);
-    for (void* p : {(void*)d_view_, (void*)d_grid_, (void*)d_pat_, (void*)d_census_})
+    for (void* p : {(void*)d_view_, (void*)d_grid_, (void*)d_pat_, (void*)d_census_, (void*)d_snap_})
         if (p) hipFree(p);
     if (h_view_) hipHostFree(h_view_);
     hipFree(d_red_);
@@ -280,12 +284,13 @@ void HipEngine::set_tile_words(const std::vector<u64>& dense) {
 
 // Census mode: the call's counts go to device slots reserved here (census_begin), in chunks of at most
 // kCensusMaxSlots generations; the kernels find their slot through census_at_ (tile_superstep, launch).
+// Signature mode records the same way, in slots of its own size (slot_words()).
 void HipEngine::run(u64 generations) {
-    if (!cfg_.census || census_mute_) return run_counted(generations);
+    if (!recording() || census_mute_) return run_counted(generations);
     while (generations > 0) {
-        const u64 n = std::min<u64>(generations, kCensusMaxSlots);
+        const u64 n = std::min<u64>(generations, max_slots());
         census_begin(n);
-        census_at_ = d_census_ + census_dev_n_ * hipk::kCensusSlotWords;
+        census_at_ = d_census_ + census_dev_n_ * slot_words();
         try {
             run_counted(n);
         } catch (...) {
@@ -308,24 +313,30 @@ void HipEngine::census_begin(u64 generations) {
     d_census_ = nullptr;
     census_cap_ = 0;
     const size_t cap = std::max<size_t>(n, 1024);
-    HIP_CHECK(hipMalloc(&d_census_, cap * kCensusSlotBytes));
+    HIP_CHECK(hipMalloc(&d_census_, cap * slot_bytes()));
     census_cap_ = cap;
-    HIP_CHECK(hipMemsetAsync(d_census_, 0, cap * kCensusSlotBytes, s_comp_));
+    HIP_CHECK(hipMemsetAsync(d_census_, 0, cap * slot_bytes(), s_comp_));
     HIP_CHECK(hipStreamSynchronize(s_comp_));
 }
 
 void HipEngine::census_collect() {
     if (census_dev_n_ == 0) return;
     synchronize();  // the passes of either stream have added their counts
-    std::vector<u64> raw(census_dev_n_ * (size_t)hipk::kCensusSlotWords);
+    std::vector<u64> raw(census_dev_n_ * slot_words());
     HIP_CHECK(hipMemcpyAsync(raw.data(), d_census_, raw.size() * sizeof(u64), hipMemcpyDeviceToHost, s_comp_));
-    HIP_CHECK(hipMemsetAsync(d_census_, 0, census_dev_n_ * kCensusSlotBytes, s_comp_));
+    HIP_CHECK(hipMemsetAsync(d_census_, 0, census_dev_n_ * slot_bytes(), s_comp_));
     HIP_CHECK(hipStreamSynchronize(s_comp_));
+    static_assert(hipk::kSigStripes == hipk::kCensusStripes && hipk::kSigStripeWords == hipk::kCensusStripeWords,
+                  "one stripe layout for the counts of both modes");
     for (size_t g = 0; g < census_dev_n_; ++g) {  // a generation's count: the sum of its slot's stripes
-        u64 sum = 0;
-        for (int st = 0; st < hipk::kCensusStripes; ++st)
-            sum += raw[g * (size_t)hipk::kCensusSlotWords + (size_t)st * hipk::kCensusStripeWords];
+        u64 sum = 0, sig = 0;
+        for (int st = 0; st < hipk::kCensusStripes; ++st) {
+            const size_t at = g * slot_words() + (size_t)st * hipk::kCensusStripeWords;
+            sum += raw[at];
+            if (cfg_.signature) sig += raw[at + hipk::kSigSigOffset];  // (wrapping)
+        }
         census_host_.push_back(sum);
+        if (cfg_.signature) sig_host_.push_back(sig);
     }
     census_dev_n_ = 0;
 }
@@ -333,9 +344,52 @@ void HipEngine::census_collect() {
 void HipEngine::census_discard() {
     if (census_dev_n_ == 0) return;
     synchronize();
-    HIP_CHECK(hipMemsetAsync(d_census_, 0, census_dev_n_ * kCensusSlotBytes, s_comp_));
+    HIP_CHECK(hipMemsetAsync(d_census_, 0, census_dev_n_ * slot_bytes(), s_comp_));
     HIP_CHECK(hipStreamSynchronize(s_comp_));
     census_dev_n_ = 0;
+}
+
+// ----- signature(), snapshot(), snapshot_diff(): this rank's part (signature_kernel.hip) -----
+
+u64 HipEngine::local_signature() {
+    sync_canonical();
+    check_res_status();
+    HIP_CHECK(hipMemsetAsync(d_red_, 0, sizeof(u64), s_comp_));
+    hipk::launch_signature(buf_[cur_], L_, g_.row0, g_.word0(), d_red_, s_comp_);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h_red_, d_red_, sizeof(u64), hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    return h_red_[0];
+}
+
+void HipEngine::snapshot_local() {
+    sync_canonical();
+    check_res_status();
+    if (!d_snap_) {
+        size_t fr = 0, tot = 0;
+        if (hipMemGetInfo(&fr, &tot) != hipSuccess || fr < alloc_bytes_ + ((size_t)64 << 20) ||
+            hipMalloc(&d_snap_, alloc_bytes_) != hipSuccess) {
+            (void)hipGetLastError();
+            d_snap_ = nullptr;
+            throw Error(strprintf("snapshot(): no device memory for a third board buffer of %zu bytes (%zu free)", alloc_bytes_, fr));
+        }
+    }
+    synchronize();  // (the passes of either stream have written the board)
+    HIP_CHECK(hipMemcpyAsync(d_snap_, buf_[cur_], alloc_bytes_, hipMemcpyDeviceToDevice, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+}
+
+u64 HipEngine::snapshot_diff_local() {
+    if (!d_snap_) throw Error("snapshot_diff(): no snapshot buffer");
+    sync_canonical();
+    check_res_status();
+    synchronize();
+    HIP_CHECK(hipMemsetAsync(d_red_, 0, sizeof(u64), s_comp_));
+    hipk::launch_board_diff(buf_[cur_], d_snap_, L_, d_red_, s_comp_);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(h_red_, d_red_, sizeof(u64), hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    return h_red_[0];
 }
 
 void HipEngine::run_counted(u64 generations) {
@@ -421,7 +475,7 @@ void HipEngine::finish_init() {
     if (!split_ && !dual_ && kern_[0] == "pipe")
         stats_.kernel = strprintf("pipe@%d(%dx%d,%d/CU)", pipe_k_, pipe_cur_.nw - 1, pipe_cur_.l, pipe_cur_.wg);
     if (rule_) {
-        const std::string rk = strprintf(cfg_.census ? "census@%d" : "rule@%d", kdepth_);
+        const std::string rk = strprintf(cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", kdepth_);
         stats_.kernel = split_ ? rk + "+boundary:" + rk : rk;
     }
     if (res_) {
@@ -448,7 +502,7 @@ void HipEngine::finish_init() {
                 const PassKernel pk = pass_kernel(kind, ps[j]);
                 c += (j ? "+" : "") + (pk == PK_PIPE   ? strprintf("pipe@%d(%dx%d,%d/CU)", ps[j], g->nw - 1, g->l, g->wg)
                                        : pk == PK_TILE ? strprintf("tile@%d", ps[j])
-                                       : pk == PK_RULE ? strprintf(cfg_.census ? "census@%d" : "rule@%d", ps[j])
+                                       : pk == PK_RULE ? strprintf(cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", ps[j])
                                                        : strprintf("temporal@%d", ps[j]));
             }
             tn += strprintf("%scut%d=%s", tn.empty() ? "" : " ", k, c.c_str());
@@ -505,7 +559,7 @@ void HipEngine::tile_superstep(int k) {
     const std::vector<int>& ps = pass_depths(k);
     first_pass(k, ps[0], ext_after(ps, 0), split_);
     cur_ ^= 1;
-    if (census_at_) census_at_ += (size_t)ps[0] * hipk::kCensusSlotWords;  // (the interior and the bands of a split pass add into the same slots)
+    if (census_at_) census_at_ += (size_t)ps[0] * slot_words();  // (the interior and the bands of a split pass add into the same slots)
     for (size_t j = 1; j < ps.size(); ++j) {
         // later passes need no halo: the ghost rows computed by the earlier passes carry the
         // neighbours' cells forward (communication-avoiding deep halos)
@@ -514,7 +568,7 @@ void HipEngine::tile_superstep(int k) {
         launch(0, ps[j], e, buf_[cur_], buf_[cur_ ^ 1], s_comp_);
         post(buf_[cur_ ^ 1], s_comp_, e);
         cur_ ^= 1;
-        if (census_at_) census_at_ += (size_t)ps[j] * hipk::kCensusSlotWords;
+        if (census_at_) census_at_ += (size_t)ps[j] * slot_words();
     }
     if (ps.size() > 1) mark_ready();  // the next exchange reads what the last pass wrote
 }
@@ -683,7 +737,9 @@ void HipEngine::launch(int kind, int k, i64 e, const u64* src, u64* dst, hipStre
             pipe_used_ = true;
         } else if (pk == PK_RULE) {
             const hipk::BoardEdges edges{g_.row0, g_.dec.H, g_.word0(), g_.dec.W};
-            if (cfg_.census)
+            if (cfg_.signature)
+                hipk::launch_step_signature(k, cfg_.rule, edges, dead_edges(), L_.w, src, dst, p.d, p.waves, sp, census_at_, s);
+            else if (cfg_.census)
                 hipk::launch_step_census(k, cfg_.rule, dead_edges() ? &edges : nullptr, L_.w, src, dst, p.d, p.waves, sp,
                                          census_at_, s);
             else if (dead_edges())

@@ -129,6 +129,11 @@ class HipEngine : public Engine {
         return {h_red_[0], h_red_[1]};
     }
 
+    // signature(), snapshot(), snapshot_diff(): this rank's part (engine_hip.hip)
+    u64 local_signature() override;
+    void snapshot_local() override;
+    u64 snapshot_diff_local() override;
+
     bool graph_shape(int& k, int& m);
 
     // Replay shapes {m supersteps of k, then one superstep of rem < k generations}, largest first:
@@ -304,14 +309,17 @@ class HipEngine : public Engine {
     // The streaming kernel of this engine: step_rule under a rule (rule_), else step_temporal.
     // (in census mode step_census, at its own depths, on either boundary)
     bool depth_ok(int k) const {
+        if (cfg_.signature) return k >= 1 && k <= hipk::max_signature_depth();
         if (cfg_.census) return k >= 1 && k <= hipk::max_census_depth();
         return rule_ ? hipk::rule_depth_supported(k) : hipk::step_depth_supported(k);
     }
     int max_depth() const {
+        if (cfg_.signature) return hipk::max_signature_depth();
         if (cfg_.census) return hipk::max_census_depth();
         return rule_ ? hipk::max_rule_depth() : hipk::max_step_depth();
     }
     int blocks_per_cu(int k, u32 flags) const {
+        if (cfg_.signature) return hipk::signature_blocks_per_cu(k, flags, dead_edges());
         if (cfg_.census) return hipk::census_blocks_per_cu(k, flags, dead_edges());
         if (dead_edges()) return hipk::rule_bounded_blocks_per_cu(k, flags);
         return rule_ ? hipk::rule_blocks_per_cu(k, flags) : hipk::step_blocks_per_cu(k, flags);
@@ -738,6 +746,12 @@ class HipEngine : public Engine {
     // Most slots the device buffer holds before run() moves them to the host (32 MiB: a slot is 16 lines, 2 KiB)
     static constexpr size_t kCensusMaxSlots = (size_t)1 << 14;
     static constexpr size_t kCensusSlotBytes = (size_t)hipk::kCensusSlotWords * sizeof(u64);
+    // Signature mode uses the same machinery with slots of kSigSlotWords words (counts, then signatures), half as
+    // many of them in the same 32 MiB.
+    size_t slot_words() const { return (size_t)(cfg_.signature ? hipk::kSigSlotWords : hipk::kCensusSlotWords); }
+    size_t slot_bytes() const { return slot_words() * sizeof(u64); }
+    size_t max_slots() const { return cfg_.signature ? kCensusMaxSlots / 2 : kCensusMaxSlots; }
+    u64* d_snap_ = nullptr;  // snapshot(): a third board buffer (alloc_bytes_), allocated on first use
     bool res_ = false;  // supersteps run the resident kernel
     int res_kin_ = 0;   // its generations per in-kernel halo exchange
     std::map<int, ResPlan> res_plans_;

@@ -169,6 +169,7 @@ EngineConfig engine_config(const Options& o, const std::string& backend, int dev
     c.rule = Rule::parse(o.rule.empty() ? env_str("GOL_RULE", "B3/S23") : o.rule);
     c.boundary = parse_boundary(o.boundary.empty() ? env_str("GOL_BOUNDARY", "torus") : o.boundary);
     c.census = o.census;
+    c.signature = o.signature;
     c.tile_waves = (int)env_int("GOL_TILE_WAVES", 8);
     c.tune_tile_waves = getenv("GOL_TILE_WAVES") == nullptr;
     c.transport = (o.transport == "rccl" || o.transport == "p2p") ? "device" : o.transport;
@@ -448,6 +449,7 @@ void write_metrics(const Options& o, Engine& eng, const CliArgs& a, double durat
     f << "  \"rule\": \"" << s.rule << "\",\n";
     f << "  \"boundary\": \"" << s.boundary << "\",\n";
     f << "  \"census\": " << (s.census ? "true" : "false") << ",\n";
+    f << "  \"signature\": " << (s.signature ? "true" : "false") << ",\n";
     f << "  \"schedule\": \"" << s.schedule << "\",\n";
     f << "  \"autotune\": \"" << s.tuning << "\",\n";
     f << "  \"plan_waves\": " << s.plan_waves << ",\n  \"lane_efficiency\": " << s.lane_efficiency << ",\n";
@@ -594,6 +596,24 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
             }
             t->broadcast(&ok, sizeof(ok), 0);
             if (!ok) throw Error("GOL_CENSUS_OUT: cannot write " + o.census_out);
+        }
+        if (!o.signature_out.empty()) {
+            // the run's series (collective); rank 0 writes it, and every rank learns whether that worked
+            const Engine::SignatureSeries ss = eng->signatures();
+            u64 ok = 1;
+            if (rank == 0) {
+                FILE* cf = fopen(o.signature_out.c_str(), "w");
+                ok = cf != nullptr;
+                if (cf) {
+                    ok = fputs("generation,population,signature\n", cf) >= 0;
+                    for (size_t i = 0; i < ss.signatures.size() && ok; ++i)
+                        ok = fprintf(cf, "%llu,%llu,%016llx\n", (unsigned long long)(ss.start + 1 + i),
+                                     (unsigned long long)ss.populations[i], (unsigned long long)ss.signatures[i]) > 0;
+                    ok = (fclose(cf) == 0) && ok;
+                }
+            }
+            t->broadcast(&ok, sizeof(ok), 0);
+            if (!ok) throw Error("GOL_SIGNATURE_OUT: cannot write " + o.signature_out);
         }
         if (!o.rle_out.empty()) {
             RlePattern out;

@@ -69,6 +69,13 @@ class Simulation:
                   ``step_census`` counts inside every pass, for every rule and either boundary (generic-kernel
                   speed, passes of at most ``max_census_depth`` generations, eager launches); without
                   ``compat``, ``subtiles=2`` or the specialised kernels.
+    signature:    signature mode (default off; GOL_SIGNATURE): every generation :meth:`step` computes also yields the
+                  board signature, a linear position-keyed 64-bit hash equal for every decomposition, and the
+                  population of that generation, read with :meth:`signatures`; :meth:`find_cycle` is built on it.
+                  HIP: the signature kernel ``step_signature`` hashes inside every pass, for every rule and either
+                  boundary (generic-kernel speed, B3/S23 included; passes of at most ``max_signature_depth``
+                  generations, eager launches); without ``census`` (it records the population already),
+                  ``compat``, ``subtiles=2`` or the specialised kernels.
     compat:       reproduce the reference's halo quirks (frozen gen-0 halos, P<=2 swap).
     watchdog:     seconds without progress before the job is aborted (0 = off; GOL_WATCHDOG).
     """
@@ -105,6 +112,7 @@ class Simulation:
         rule: str = os.environ.get("GOL_RULE", "B3/S23"),
         boundary: Optional[str] = None,
         census: Optional[bool] = None,
+        signature: Optional[bool] = None,
     ):
         self.transport = transport if transport is not None else _gol.SelfTransport()
         P, rank = self.transport.size(), self.transport.rank()
@@ -151,6 +159,23 @@ class Simulation:
                 raise ValueError(
                     f"census=True: kernel_depth {kernel_depth} exceeds the census kernel's deepest pass, "
                     f"{_gol.max_census_depth()} generations"
+                )
+        if signature is None:  # (read per call, as the census mode is)
+            signature = os.environ.get("GOL_SIGNATURE", "0").lower() in ("1", "true", "yes", "on")
+        cfg.signature = bool(signature)
+        if cfg.signature:
+            if cfg.census:
+                raise ValueError("signature=True with census=True: signature mode already records the population")
+            if compat:
+                raise ValueError("signature=True with compat=True: compat mode runs the reference's loop, not the signature kernel")
+            if int(subtiles) == 2:
+                raise ValueError("signature=True with subtiles=2: the sub-tile halves do not run the signature kernel")
+            if self.backend == "hip" and kernel in ("temporal", "tile", "pipe", "resident", "lds"):
+                raise ValueError(f"kernel {kernel!r} records no signatures: the signature kernel runs every pass (use auto or rule)")
+            if self.backend == "hip" and int(kernel_depth) > _gol.max_signature_depth():
+                raise ValueError(
+                    f"signature=True: kernel_depth {kernel_depth} exceeds the signature kernel's deepest pass, "
+                    f"{_gol.max_signature_depth()} generations"
                 )
         cfg.subtiles = int(subtiles)  # 2 / 0 / -1 auto: two sub-tiles per rank on two streams (HIP, 1-D)
         cfg.run_hint = int(run_hint)  # generations of the runs to come: one replay graph covers them
@@ -239,6 +264,80 @@ class Simulation:
     def fingerprint(self) -> int:
         """Decomposition-invariant fingerprint of the global board (collective)."""
         return int(self.engine.fingerprint())
+
+    def signature(self) -> int:
+        """The board signature of the current global board (collective; any mode): the linear, position-keyed 64-bit
+        hash that signature mode records for every generation (:func:`ops.numpy_signature` is its oracle)."""
+        return int(self.engine.signature())
+
+    def signatures(self):
+        """``(start, signatures, populations)``: entry ``i`` of the two uint64 arrays is the board signature and the
+        global population at generation ``start + 1 + i``, one entry per generation computed since the record was
+        cleared (by :meth:`init`, :meth:`load_rle`, :meth:`restore` or :meth:`signatures_clear`; :meth:`stamp` leaves it
+        running).  Collective; every rank gets the same arrays.  Needs ``signature=True``."""
+        if not self.config.signature:
+            raise ValueError("signatures() needs a simulation built with signature=True (or GOL_SIGNATURE=1)")
+        start, sigs, pops = self.engine.signatures()
+        return int(start), sigs, pops
+
+    def signatures_clear(self) -> None:
+        """Forget the recorded series; the next one starts at the generation reached."""
+        if not self.config.signature:
+            raise ValueError("signatures_clear() needs a simulation built with signature=True (or GOL_SIGNATURE=1)")
+        self.engine.signatures_clear()
+
+    def snapshot(self) -> None:
+        """Keep a copy of the current board (a third board buffer, allocated on first use) for :meth:`snapshot_diff`."""
+        self.engine.snapshot()
+
+    def snapshot_diff(self) -> int:
+        """The number of cells of the global board that differ from the last :meth:`snapshot` (collective)."""
+        return int(self.engine.snapshot_diff())
+
+    def find_cycle(self, max_generations: int, chunk: int = 256):
+        """Step the board until it repeats: ``None`` when it has not within ``max_generations`` generations from the
+        current one, else a :class:`ops.Cycle` ``(transient, period, generation, population)``: the board entered its
+        cycle at generation ``transient`` (of the simulation's generation counter; the search starts at the current
+        generation, so call it at generation 0 for the transient of the initial board), repeats every ``period``
+        generations, and now stands at ``generation``, on the cycle, with ``population`` live cells.  Collective;
+        every rank returns the same value.  Needs ``signature=True``.
+
+        The board is stepped ``chunk`` generations at a time and each generation's signature looked up among the
+        earlier ones.  A hit is confirmed on the device, cell by cell: the board is copied, stepped one candidate
+        period further and compared.  So the period and the membership of the final board in the cycle are exact,
+        whatever the hash does (a collision is dropped and the search goes on); the transient rests on the 64-bit
+        signatures telling the generations before it apart.  The record of :meth:`signatures` is consumed.  The
+        confirmation may step up to one period beyond ``max_generations``."""
+        from ..ops.cycle import Cycle, find_repeat
+
+        if not self.config.signature:
+            raise ValueError("find_cycle() needs a simulation built with signature=True (or GOL_SIGNATURE=1)")
+        max_generations, chunk = int(max_generations), int(chunk)
+        if max_generations < 1 or chunk < 1:
+            raise ValueError(f"find_cycle: max_generations and chunk must be >= 1, got {max_generations}, {chunk}")
+        g0 = self.generation
+        end = g0 + max_generations
+        self.signatures_clear()
+        seen = {self.signature(): g0}
+
+        def verify(g_prev: int, g: int) -> bool:
+            # the board stands at some G >= g: board(G) == board(G + p) proves the period (and G on the cycle)
+            self.snapshot()
+            self.step(g - g_prev)
+            return self.snapshot_diff() == 0
+
+        read_to = g0  # the generation the series has been searched up to
+        while True:
+            if self.generation == read_to:  # (else: generations stepped by a rejected confirmation are still unread)
+                if read_to >= end:
+                    return None
+                self.step(min(chunk, end - read_to))
+            start, sigs, _ = self.signatures()
+            self.signatures_clear()
+            read_to = start + len(sigs)
+            hit = find_repeat(sigs, seen, start + 1, verify)
+            if hit is not None:
+                return Cycle(hit[0], hit[1] - hit[0], self.generation, self.population())
 
     def stats(self) -> dict:
         return self.engine.stats()

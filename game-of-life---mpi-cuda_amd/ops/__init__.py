@@ -4,6 +4,8 @@ from .bitpack import pack_cells, unpack_words  # noqa: F401
 from .oracle import (  # noqa: F401
     initial_board,
     numpy_census,
+    numpy_signature,
+    numpy_signatures,
     numpy_step,
     numpy_step_rule,
     numpy_step_rule_bounded,
@@ -14,6 +16,7 @@ from .oracle import (  # noqa: F401
     torch_step,
     torch_step_rule,
 )
+from .cycle import Cycle, find_repeat  # noqa: F401
 from .rle import parse_rle, pattern_cells, pattern_from_cells, write_rle  # noqa: F401
 from .._native import _gol as _native
 

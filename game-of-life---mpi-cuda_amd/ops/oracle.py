@@ -143,6 +143,51 @@ def numpy_census(board: np.ndarray, rule, gens: int, bounded: bool = False, retu
     return (counts, b) if return_board else counts
 
 
+def _sig_mix32(x: np.ndarray) -> np.ndarray:
+    x = x.astype(np.uint64) & np.uint64(0xFFFFFFFF)
+    m = np.uint64(0xFFFFFFFF)
+    x ^= x >> np.uint64(16)
+    x = (x * np.uint64(0x7FEB352D)) & m
+    x ^= x >> np.uint64(15)
+    x = (x * np.uint64(0x846CA68B)) & m
+    x ^= x >> np.uint64(16)
+    return x
+
+
+def numpy_signature(board: np.ndarray) -> int:
+    """The board signature of a 2-D 0/1 array (the oracle of ``signature()`` and of signature mode), from cells, not
+    from packed words: a live cell at row ``r``, column ``x`` adds ``2**((x % 64) // 2) * (rho(r) * gam(2 * (x // 64) +
+    x % 2) mod 2**32)``, the sum taken mod ``2**64``, with ``rho(r) = mix32(r ^ 0x9E3779B9) | 1`` and ``gam(j) =
+    mix32(j + 0x7F4A7C15) | 1``."""
+    b = np.asarray(board)
+    if b.ndim != 2:
+        raise ValueError("numpy_signature takes a 2-D board")
+    m = np.uint64(0xFFFFFFFF)
+    rows = np.arange(b.shape[0], dtype=np.uint64)
+    cols = np.arange(b.shape[1], dtype=np.uint64)
+    rho = _sig_mix32((rows & m) ^ np.uint64(0x9E3779B9)) | np.uint64(1)
+    gam = _sig_mix32((np.uint64(2) * (cols // np.uint64(64)) + (cols & np.uint64(1)) + np.uint64(0x7F4A7C15)) & m) | np.uint64(1)
+    shift = (cols % np.uint64(64)) // np.uint64(2)
+    r, c = np.nonzero(b)
+    key = (rho[r] * gam[c]) & m  # (< 2**64: both factors are below 2**32)
+    with np.errstate(over="ignore"):
+        terms = key << shift[c]  # (key < 2**32, shift <= 31: no bit is lost)
+        return int(terms.sum(dtype=np.uint64))  # wraps mod 2**64
+
+
+def numpy_signatures(board: np.ndarray, rule, gens: int, bounded: bool = False, return_board: bool = False):
+    """The signatures after generations ``1 .. gens`` of ``board`` under ``rule`` as a uint64 array (the oracle of the
+    engines' signature mode), on the torus or, ``bounded``, on a board with dead edges.  ``return_board`` also returns
+    the last board."""
+    step = numpy_step_rule_bounded if bounded else numpy_step_rule
+    b = np.asarray(board, dtype=np.uint8)
+    sigs = np.zeros(int(gens), dtype=np.uint64)
+    for g in range(int(gens)):
+        b = step(b, rule, 1)
+        sigs[g] = numpy_signature(b)
+    return (sigs, b) if return_board else sigs
+
+
 def torch_step_rule(board, rule, generations: int = 1, device=None):
     """A life-like rule on a torus with torch conv2d (fp32, exact for counts <= 8).  Returns a torch uint8 tensor."""
     import torch
