@@ -5,6 +5,8 @@
 //                       streaming, bit-sliced v_bitop3/v_alignbit adders, DPP wave_shr/shl lane
 //                       exchange, K-deep register pipeline (temporal blocking), periodic wrap by
 //                       load addressing.  Replaces gol_kernel + the per-generation sync/swap.
+//   The four generic-rule kernels share one streaming wave (rule_runner.hpp: the rule gates, the level loop, the
+//   runner, the edge and ownership masks) and one set of host-side checks (rule_launch.hpp); each adds a policy:
 //   step_rule<K>      — step_temporal's streaming wave with a generic finish: any B0-free life-like rule
 //                       B.../S... from two run-time masks (rule_kernel.hip; K = 1..8).
 //   step_rule_bounded<K> — step_rule on a bounded board (dead cells beyond the global edges): the loaded row and
@@ -82,8 +84,9 @@ int max_step_depth();
 void launch_step(int k, const u64* src, u64* dst, const LaneDesc* plan, i64 n_waves, const StepParams& p,
                  hipStream_t s);
 // step_rule<K> (rule_kernel.hip): K generations of `rule` over the waves of `plan`, the same plans and
-// StepParams as launch_step (STEP_SEAM excepted: it has no seam-reading variant).  It reads and writes
-// exactly the rows and words step_temporal<K> does for the same plan.  Depths 1 .. max_rule_depth().
+// StepParams as launch_step (STEP_SEAM excepted: it has no seam-reading variant).  It and the three kernels
+// below read and write exactly the rows and words step_temporal<K> does for the same plan (rule_runner.hpp
+// states the invariant once for all four).  Depths 1 .. max_rule_depth().
 bool rule_depth_supported(int k);
 int max_rule_depth();
 int rule_blocks_per_cu(int k, u32 flags);
