@@ -16,6 +16,10 @@
 //   step_signature<K> — step_census that also hashes the tile after every generation of the pass: the linear,
 //                       position-keyed board signature, two multiplies and two 64-bit multiply-adds per word and
 //                       level (signature_kernel.hip; K = 1..8; with k_signature and k_board_diff).
+//   Under a von Neumann or hexagonal rule (Rule::nbhd) the launchers of these four dispatch to the same streaming
+//   wave with that neighbourhood's gates (nbhd_gates.hpp; instantiated in nbhd_rule_kernel.hip, nbhd_bounded_kernel.hip,
+//   nbhd_census_kernel.hip, nbhd_signature_kernel.hip; K = 1..8): the depth and occupancy queries below take the
+//   neighbourhood for that reason.
 //   step_lds          — single-generation LDS-tiled variant (tile + ghost words staged in LDS);
 //                       kept as a measured alternative (GOL_KERNEL=lds).
 //   fill_ghost_cols   — x-periodic ghost words for widths that are not a multiple of 64.
@@ -87,9 +91,9 @@ void launch_step(int k, const u64* src, u64* dst, const LaneDesc* plan, i64 n_wa
 // StepParams as launch_step (STEP_SEAM excepted: it has no seam-reading variant).  It and the three kernels
 // below read and write exactly the rows and words step_temporal<K> does for the same plan (rule_runner.hpp
 // states the invariant once for all four).  Depths 1 .. max_rule_depth().
-bool rule_depth_supported(int k);
-int max_rule_depth();
-int rule_blocks_per_cu(int k, u32 flags);
+bool rule_depth_supported(int k, Nbhd nbhd = Nbhd::Moore);
+int max_rule_depth(Nbhd nbhd = Nbhd::Moore);
+int rule_blocks_per_cu(int k, u32 flags, Nbhd nbhd = Nbhd::Moore);
 void launch_step_rule(int k, const Rule& rule, const u64* src, u64* dst, const LaneDesc* plan, i64 n_waves,
                       const StepParams& p, hipStream_t s);
 // step_rule_bounded<K> (rule_bounded_kernel.hip): step_rule on a bounded board (Boundary::Dead).  Cells outside
@@ -101,7 +105,7 @@ struct BoardEdges {
     i64 word0 = 0;  // global word index of tile word 0
     i64 cols = 0;   // columns of the global board
 };
-int rule_bounded_blocks_per_cu(int k, u32 flags);
+int rule_bounded_blocks_per_cu(int k, u32 flags, Nbhd nbhd = Nbhd::Moore);
 void launch_step_rule_bounded(int k, const Rule& rule, const BoardEdges& edges, const u64* src, u64* dst,
                               const LaneDesc* plan, i64 n_waves, const StepParams& p, hipStream_t s);
 // step_census<K> (census_kernel.hip): step_rule (edges == nullptr: the torus) or step_rule_bounded (edges) that also
@@ -113,8 +117,8 @@ void launch_step_rule_bounded(int k, const Rule& rule, const BoardEdges& edges, 
 // launch_step_rule_bounded.  Depths 1 .. max_census_depth().
 constexpr int kCensusStripes = 16, kCensusStripeWords = 16;
 constexpr int kCensusSlotWords = kCensusStripes * kCensusStripeWords;  // u64 words from one generation's slot to the next
-int max_census_depth();
-int census_blocks_per_cu(int k, u32 flags, bool bounded);
+int max_census_depth(Nbhd nbhd = Nbhd::Moore);
+int census_blocks_per_cu(int k, u32 flags, bool bounded, Nbhd nbhd = Nbhd::Moore);
 void launch_step_census(int k, const Rule& rule, const BoardEdges* edges, i64 tile_cols, const u64* src, u64* dst,
                         const LaneDesc* plan, i64 n_waves, const StepParams& p, u64* counts, hipStream_t s);
 // step_signature<K> (signature_kernel.hip): step_census that also adds each generation's share of the board
@@ -127,8 +131,8 @@ void launch_step_census(int k, const Rule& rule, const BoardEdges* edges, i64 ti
 constexpr int kSigStripes = 16, kSigStripeWords = 16;
 constexpr int kSigSigOffset = kSigStripes * kSigStripeWords;  // u64 words from a slot's counts to its signatures
 constexpr int kSigSlotWords = 2 * kSigSigOffset;              // u64 words from one generation's slot to the next
-int max_signature_depth();
-int signature_blocks_per_cu(int k, u32 flags, bool bounded);
+int max_signature_depth(Nbhd nbhd = Nbhd::Moore);
+int signature_blocks_per_cu(int k, u32 flags, bool bounded, Nbhd nbhd = Nbhd::Moore);
 void launch_step_signature(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src,
                            u64* dst, const LaneDesc* plan, i64 n_waves, const StepParams& p, u64* slots, hipStream_t s);
 // out[0] += the signature of the tile in `buf` at (grow0, gword0) (wrapping; out zeroed by the caller).

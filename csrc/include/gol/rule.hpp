@@ -1,7 +1,13 @@
-// gol-mi355x: life-like rules (outer-totalistic, radius-1 Moore neighbourhood, two states).
+// gol-mi355x: life-like rules (outer-totalistic, radius 1, two states) on the Moore, von Neumann or hexagonal
+// neighbourhood.
 //
-// A rule is two 9-bit masks: bit c (0..8) of `birth` / `survive` says that a dead / live cell with c
-// live neighbours is alive in the next generation.  Conway's Life is B3/S23 = {0x008, 0x00C}.
+// A rule is two 9-bit masks and a neighbourhood: bit c (0..8) of `birth` / `survive` says that a dead / live
+// cell with c live neighbours is alive in the next generation.  Conway's Life is B3/S23 = {0x008, 0x00C}.
+// The neighbours counted, as 3 x 3 masks around the centre (rows downward, columns rightward):
+//   Moore (no suffix)   von Neumann (V)   hexagonal (H: the square-grid emulation without NE and SW)
+//       1 1 1               0 1 0             1 1 0
+//       1 . 1               1 . 1             1 . 1
+//       1 1 1               0 1 0             0 1 1
 //
 // B0 rules are refused: with B0 the infinite dead background comes alive, and the engine's zeroed slack
 // rows, trash lanes and masked tail bits all assume that dead stays dead where nothing is stored.
@@ -15,22 +21,38 @@ namespace gol {
 
 using u16 = uint16_t;
 
+enum class Nbhd : u16 { Moore = 0, VonNeumann = 1, Hex = 2 };
+
+// The largest neighbour count of a neighbourhood: 8, 4, 6.
+constexpr int nbhd_max_count(Nbhd n) { return n == Nbhd::VonNeumann ? 4 : (n == Nbhd::Hex ? 6 : 8); }
+// The rule-string suffix: "", "V", "H".
+constexpr const char* nbhd_suffix(Nbhd n) { return n == Nbhd::VonNeumann ? "V" : (n == Nbhd::Hex ? "H" : ""); }
+const char* nbhd_name(Nbhd n);  // "Moore", "von Neumann", "hexagonal"
+
 struct Rule {
     u16 birth = 1u << 3;
     u16 survive = (1u << 2) | (1u << 3);
+    Nbhd nbhd = Nbhd::Moore;
 
-    // "B<digits>/S<digits>" or "S<digits>/B<digits>" (letters in either case, digits 0..8 without
-    // repeats, either list may be empty), or an alias: conway, life, highlife, daynight, seeds,
-    // replicator.  Throws gol::Error naming the string on anything else, and on every rule with B0.
+    // "B<digits>/S<digits>[V|H]" or "S<digits>/B<digits>[V|H]" (letters in either case, digits without repeats
+    // from 0 to the neighbourhood's largest count -- 8, V: 4, H: 6 --, either list may be empty), or an alias:
+    // conway, life, highlife, daynight, seeds, replicator.  Throws gol::Error naming the string on anything else,
+    // and on every rule with B0.
     static Rule parse(const std::string& s);
-    // Masks -> rule, with the same range and B0 checks as parse (bindings, checkpoints).
+    // Masks -> rule, with the same range and B0 checks as parse (bindings, checkpoints).  Two arguments: Moore.
     static Rule from_masks(unsigned birth, unsigned survive);
-    // Canonical form: B<digits>/S<digits>, digits ascending.
+    static Rule from_masks(unsigned birth, unsigned survive, Nbhd nbhd);
+    // code() -> rule, checked as from_masks.
+    static Rule from_code(u32 code);
+    // Canonical form: B<digits>/S<digits>, digits ascending, then V or H (nothing for Moore).
     std::string str() const;
-    bool is_conway() const { return birth == (1u << 3) && survive == ((1u << 2) | (1u << 3)); }
-    // birth | survive << 16 (checkpoint header, rank agreement)
-    u32 code() const { return (u32)birth | ((u32)survive << 16); }
-    bool operator==(const Rule& o) const { return birth == o.birth && survive == o.survive; }
+    bool is_conway() const {
+        return birth == (1u << 3) && survive == ((1u << 2) | (1u << 3)) && nbhd == Nbhd::Moore;
+    }
+    // birth | neighbourhood << 12 | survive << 16 (checkpoint header, rank agreement).  The neighbourhood lies in
+    // bits no Moore code has set: a code written before there were neighbourhoods reads as Moore.
+    u32 code() const { return (u32)birth | ((u32)nbhd << 12) | ((u32)survive << 16); }
+    bool operator==(const Rule& o) const { return birth == o.birth && survive == o.survive && nbhd == o.nbhd; }
     bool operator!=(const Rule& o) const { return !(*this == o); }
 };
 

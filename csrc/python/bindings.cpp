@@ -305,6 +305,15 @@ PYBIND11_MODULE(_gol, m) {
             throw py::value_error(e.what());
         }
     });
+    // rule string -> (birth, survive, neighbourhood suffix): "" Moore, "V" von Neumann, "H" hexagonal
+    m.def("parse_rule_nbhd", [](const std::string& s) {
+        try {
+            const Rule r = Rule::parse(s);
+            return py::make_tuple((unsigned)r.birth, (unsigned)r.survive, std::string(nbhd_suffix(r.nbhd)));
+        } catch (const Error& e) {
+            throw py::value_error(e.what());
+        }
+    });
 
     py::class_<Engine>(m, "Engine")
         .def_static(

@@ -17,14 +17,31 @@ const char* kB0Text =
 
 }  // namespace
 
-Rule Rule::from_masks(unsigned birth, unsigned survive) {
-    const std::string name = strprintf("(birth 0x%x, survive 0x%x)", birth, survive);
-    if (birth > 0x1FFu || survive > 0x1FFu) bad(name, "neighbour counts run from 0 to 8");
+const char* nbhd_name(Nbhd n) {
+    return n == Nbhd::VonNeumann ? "von Neumann" : (n == Nbhd::Hex ? "hexagonal" : "Moore");
+}
+
+Rule Rule::from_masks(unsigned birth, unsigned survive) { return from_masks(birth, survive, Nbhd::Moore); }
+
+Rule Rule::from_masks(unsigned birth, unsigned survive, Nbhd nbhd) {
+    if ((unsigned)nbhd > (unsigned)Nbhd::Hex)
+        bad(strprintf("(birth 0x%x, survive 0x%x)", birth, survive), strprintf("unknown neighbourhood %u", (unsigned)nbhd));
+    const std::string name = nbhd == Nbhd::Moore
+                                 ? strprintf("(birth 0x%x, survive 0x%x)", birth, survive)
+                                 : strprintf("(birth 0x%x, survive 0x%x, %s)", birth, survive, nbhd_name(nbhd));
+    const unsigned top = (2u << nbhd_max_count(nbhd)) - 1u;
+    if (birth > top || survive > top) bad(name, strprintf("neighbour counts run from 0 to %d", nbhd_max_count(nbhd)));
     if (birth & 1u) bad(name, kB0Text);
     Rule r;
     r.birth = (u16)birth;
     r.survive = (u16)survive;
+    r.nbhd = nbhd;
     return r;
+}
+
+Rule Rule::from_code(u32 code) {
+    if (code & 0xC000u) bad(strprintf("(code 0x%x)", code), "unknown neighbourhood");
+    return from_masks(code & 0x0FFFu, (code >> 16) & 0xFFFFu, (Nbhd)((code >> 12) & 3u));
 }
 
 Rule Rule::parse(const std::string& s) {
@@ -58,11 +75,18 @@ Rule Rule::parse(const std::string& s) {
             mask[which] |= 1u << d;
         }
     }
+    Nbhd nbhd = Nbhd::Moore;  // the suffix, directly after the second list
+    if (i < low.size() && (low[i] == 'v' || low[i] == 'h')) nbhd = low[i++] == 'v' ? Nbhd::VonNeumann : Nbhd::Hex;
     if (i != low.size()) bad(s, "trailing text '" + s.substr(i) + "'");
+    const int top = nbhd_max_count(nbhd);
+    for (int d = top + 1; d <= 8; ++d)
+        if ((mask[0] | mask[1]) & (1u << d))
+            bad(s, strprintf("digit %d: %s neighbour counts run from 0 to %d", d, nbhd_name(nbhd), top));
     if (mask[0] & 1u) bad(s, kB0Text);
     Rule r;
     r.birth = (u16)mask[0];
     r.survive = (u16)mask[1];
+    r.nbhd = nbhd;
     return r;
 }
 
@@ -73,7 +97,7 @@ std::string Rule::str() const {
     out += "/S";
     for (int d = 0; d <= 8; ++d)
         if (survive & (1u << d)) out += (char)('0' + d);
-    return out;
+    return out + nbhd_suffix(nbhd);
 }
 
 }  // namespace gol

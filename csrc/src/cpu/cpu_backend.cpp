@@ -43,7 +43,65 @@ inline u64 rule64_generic(u64 a0, u64 a1, u64 b0, u64 b1, u64 c0, u64 c1, u64 x,
     return mux64(x, tree64(f.s, x0, t1, t2, t3), tree64(f.b, x0, t1, t2, t3));
 }
 
+// The von Neumann and hexagonal neighbourhoods (rule.hpp): the neighbours are whole words here -- the rows above and
+// below as they are, and every cell's west / east neighbour gathered into its own bit position -- counted one by one
+// into a three-plane counter (0..6), and the rule is decoded count by count:  next = OR over c of
+// [count == c] & (x ? S[c] : B[c]).  The count excludes the centre.
+// Split format: the west neighbour of an even cell is the odd cell before it (the odd half shifted up, bit 0 from
+// the previous word), that of an odd cell the even cell of the same bit; east is the mirror image.
+inline u64 west64(u64 prev, u64 cur) {
+    const u32 lo = (u32)cur, hi = (u32)(cur >> 32), prevhi = (u32)(prev >> 32);
+    return (u64)((hi << 1) | (prevhi >> 31)) | ((u64)lo << 32);
+}
+inline u64 east64(u64 cur, u64 next) {
+    const u32 lo = (u32)cur, hi = (u32)(cur >> 32), nextlo = (u32)next;
+    return (u64)hi | ((u64)((lo >> 1) | (nextlo << 31)) << 32);
+}
+
+struct Count3 {
+    u64 n0 = 0, n1 = 0, n2 = 0;
+    void add(u64 v) {
+        const u64 c0 = n0 & v, c1 = n1 & c0;
+        n0 ^= v;
+        n1 ^= c0;
+        n2 ^= c1;
+    }
+    u64 is(int c) const { return (c & 1 ? n0 : ~n0) & (c & 2 ? n1 : ~n1) & (c & 4 ? n2 : ~n2); }
+};
+
+void step_rows_nbhd(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, const Rule& rule) {
+    const bool hex = rule.nbhd == Nbhd::Hex;
+    const int top = nbhd_max_count(rule.nbhd);
+    const i64 n = L.nw + 2;  // words -1 .. nw
+#pragma omp parallel for schedule(static) if ((r_hi - r_lo) * n > 16384)
+    for (i64 r = r_lo; r < r_hi; ++r) {
+        const u64* up = src + L.index(r - 1, -1);
+        const u64* mid = src + L.index(r, -1);
+        const u64* dn = src + L.index(r + 1, -1);
+        u64* out = dst + L.index(r, -1);
+        for (i64 j = 0; j < n; ++j) {
+            Count3 cnt;
+            cnt.add(up[j]);                                      // N
+            cnt.add(dn[j]);                                      // S
+            cnt.add(west64(j ? mid[j - 1] : 0, mid[j]));         // W
+            cnt.add(east64(mid[j], j + 1 < n ? mid[j + 1] : 0));  // E
+            if (hex) {
+                cnt.add(west64(j ? up[j - 1] : 0, up[j]));          // NW
+                cnt.add(east64(dn[j], j + 1 < n ? dn[j + 1] : 0));  // SE
+            }
+            const u64 x = mid[j];
+            u64 next = 0;
+            for (int c = 0; c <= top; ++c) {
+                const u64 born = (rule.birth >> c) & 1u ? ~x : 0, stays = (rule.survive >> c) & 1u ? x : 0;
+                next |= cnt.is(c) & (born | stays);
+            }
+            out[j] = next;
+        }
+    }
+}
+
 void step_rows_generic(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, const Rule& rule) {
+    if (rule.nbhd != Nbhd::Moore) return step_rows_nbhd(src, dst, L, r_lo, r_hi, rule);
     const RuleLeaves f(rule);
     const i64 n = L.nw + 2;  // words -1 .. nw
 #pragma omp parallel for schedule(static) if ((r_hi - r_lo) * n > 16384)

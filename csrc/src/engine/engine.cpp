@@ -22,7 +22,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     : g_(g), cfg_(c), t_(std::move(t)) {
     if (!t_) throw Error("engine needs a transport");
     xchg_self_ = cfg_.self_exchange && !cfg_.compat;
-    Rule::from_masks(cfg_.rule.birth, cfg_.rule.survive);  // (a rule set by its masks: range and B0 checks)
+    Rule::from_masks(cfg_.rule.birth, cfg_.rule.survive, cfg_.rule.nbhd);  // (a rule set by its masks: range and B0 checks)
     if (!cfg_.rule.is_conway()) {
         const std::string rs = cfg_.rule.str();
         if (cfg_.compat) throw Error("GOL_COMPAT=reference with rule " + rs + ": the reference has one rule, B3/S23");

@@ -309,20 +309,20 @@ class HipEngine : public Engine {
     // The streaming kernel of this engine: step_rule under a rule (rule_), else step_temporal.
     // (in census mode step_census, at its own depths, on either boundary)
     bool depth_ok(int k) const {
-        if (cfg_.signature) return k >= 1 && k <= hipk::max_signature_depth();
-        if (cfg_.census) return k >= 1 && k <= hipk::max_census_depth();
-        return rule_ ? hipk::rule_depth_supported(k) : hipk::step_depth_supported(k);
+        if (cfg_.signature) return k >= 1 && k <= hipk::max_signature_depth(cfg_.rule.nbhd);
+        if (cfg_.census) return k >= 1 && k <= hipk::max_census_depth(cfg_.rule.nbhd);
+        return rule_ ? hipk::rule_depth_supported(k, cfg_.rule.nbhd) : hipk::step_depth_supported(k);
     }
     int max_depth() const {
-        if (cfg_.signature) return hipk::max_signature_depth();
-        if (cfg_.census) return hipk::max_census_depth();
-        return rule_ ? hipk::max_rule_depth() : hipk::max_step_depth();
+        if (cfg_.signature) return hipk::max_signature_depth(cfg_.rule.nbhd);
+        if (cfg_.census) return hipk::max_census_depth(cfg_.rule.nbhd);
+        return rule_ ? hipk::max_rule_depth(cfg_.rule.nbhd) : hipk::max_step_depth();
     }
     int blocks_per_cu(int k, u32 flags) const {
-        if (cfg_.signature) return hipk::signature_blocks_per_cu(k, flags, dead_edges());
-        if (cfg_.census) return hipk::census_blocks_per_cu(k, flags, dead_edges());
-        if (dead_edges()) return hipk::rule_bounded_blocks_per_cu(k, flags);
-        return rule_ ? hipk::rule_blocks_per_cu(k, flags) : hipk::step_blocks_per_cu(k, flags);
+        if (cfg_.signature) return hipk::signature_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
+        if (cfg_.census) return hipk::census_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
+        if (dead_edges()) return hipk::rule_bounded_blocks_per_cu(k, flags, cfg_.rule.nbhd);
+        return rule_ ? hipk::rule_blocks_per_cu(k, flags, cfg_.rule.nbhd) : hipk::step_blocks_per_cu(k, flags);
     }
     int supported_kernel_depth(int want) const {
         while (want > 1 && !depth_ok(want)) --want;

@@ -38,50 +38,12 @@
 //
 // Depths K = 1 .. 8, both row modes, both boundaries; registers: docs/PERFORMANCE.md section 21.
 #include "rule_launch.hpp"
+#include "rule_policies.hpp"
 
 namespace gol {
 namespace hipk {
 
 namespace {
-
-template <int K, int MASK, bool BOUNDED>
-struct CensusPolicy {
-    static constexpr int kRowBarriers = 2;
-    EdgeMask<MASK> em;  // BOUNDED
-    OwnMask<MASK> own;
-    using Tally = CountTally<K>;
-
-    __device__ __forceinline__ CensusPolicy(const LaneDesc& d, int nrows, const StepParams& p, const TileArgs& ta) {
-        const bool stores = d.flags & LANE_STORE;  // (ahead of the masks: the prologue's order, PERFORMANCE.md section 23)
-        if (BOUNDED) em.template init<K>(d, ta);
-        own.template init<K>(stores, d, nrows, p, ta);
-    }
-
-    // (BOUNDED) the loaded row: ghost rows and words hold the torus neighbour's cells
-    __device__ __forceinline__ void input(u32& lo, u32& hi, int i) const {
-        if (BOUNDED) em.apply(lo, hi, i);
-    }
-    // the (masked) output of level l is counted into acc[l]
-    __device__ __forceinline__ void level(Tally& ty, int l, u32& lo, u32& hi, int t) const {
-        if (BOUNDED) em.apply(lo, hi, t);
-        const u32 r = own.row(t);
-        ty.acc[l] = (u32)__builtin_popcount(b3<kLutAnd3>(hi, own.own_hi, r)) + ty.acc[l];
-        ty.acc[l] = (u32)__builtin_popcount(b3<kLutAnd3>(lo, own.own_lo, r)) + ty.acc[l];
-    }
-    // The wave's count of each level: summed over the lanes, one 64-bit atomic per level from lane 0.
-    __device__ __forceinline__ void finish(const Tally& ty, i64 wave_id, u64* counts) const {
-        if (!counts) return;
-        const size_t stripe = (size_t)(wave_id & (kCensusStripes - 1)) * kCensusStripeWords;
-#pragma unroll
-        for (int l = 0; l < K; ++l) {
-            u32 v = ty.acc[l];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-            if ((threadIdx.x & 63) == 0 && v != 0)
-                atomicAdd(reinterpret_cast<unsigned long long*>(counts + (size_t)l * kCensusSlotWords + stripe), (unsigned long long)v);
-        }
-    }
-};
 
 template <int K, int ROWS, bool BOUNDED>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void step_census(const u64* __restrict__ src, u64* __restrict__ dst,
@@ -104,7 +66,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void step_census(const u64* __
     }
 }
 
-const void* census_kernel_of(int k, u32 flags, bool bounded) {
+const void* census_kernel_of(Nbhd nbhd, int k, u32 flags, bool bounded) {
+    if (nbhd != Nbhd::Moore) return nbhd_census_kernel(nbhd, k, flags, bounded);
     return kernel_of(k, flags, [bounded](auto K, auto ROWS) {
         return bounded ? (const void*)step_census<K(), ROWS(), true> : (const void*)step_census<K(), ROWS(), false>;
     });
@@ -112,9 +75,11 @@ const void* census_kernel_of(int k, u32 flags, bool bounded) {
 
 }  // namespace
 
-int max_census_depth() { return kMaxRuleDepth; }
+int max_census_depth(Nbhd) { return kMaxRuleDepth; }
 
-int census_blocks_per_cu(int k, u32 flags, bool bounded) { return blocks_per_cu(census_kernel_of(k, flags, bounded)); }
+int census_blocks_per_cu(int k, u32 flags, bool bounded, Nbhd nbhd) {
+    return blocks_per_cu(census_kernel_of(nbhd, k, flags, bounded));
+}
 
 void launch_step_census(int k, const Rule& rule, const BoardEdges* edges, i64 tile_cols, const u64* src, u64* dst,
                         const LaneDesc* plan, i64 n_waves, const StepParams& p, u64* counts, hipStream_t s) {
@@ -122,7 +87,7 @@ void launch_step_census(int k, const Rule& rule, const BoardEdges* edges, i64 ti
     check_rule_masks("step_census", rule);
     if (edges) check_place("step_census", *edges);
     check_tile_cols("step_census", tile_cols, p);
-    const void* f = census_kernel_of(k, p.flags, edges != nullptr);
+    const void* f = census_kernel_of(rule.nbhd, k, p.flags, edges != nullptr);
     if (!f) throw Error(strprintf("no census kernel instantiated for depth %d (1..%d)", k, kMaxRuleDepth));
     launch_generic("census", f, rule, src, dst, plan, n_waves, p, s, tile_args(edges, tile_cols, p), counts);
 }

@@ -10,25 +10,12 @@
 //
 // Depths K = 1 .. 8, both row modes, as step_rule.
 #include "rule_launch.hpp"
+#include "rule_policies.hpp"
 
 namespace gol {
 namespace hipk {
 
 namespace {
-
-template <int K, int MASK>
-struct EdgePolicy {
-    static constexpr int kRowBarriers = 2;
-    EdgeMask<MASK> em;
-
-    __device__ __forceinline__ EdgePolicy(const LaneDesc& d, int, const StepParams&, const TileArgs& ta) {
-        em.template init<K>(d, ta);
-    }
-    // the loaded row: ghost rows and ghost words hold the torus neighbour's cells
-    __device__ __forceinline__ void input(u32& lo, u32& hi, int i) const { em.apply(lo, hi, i); }
-    struct Tally {};
-    __device__ __forceinline__ void level(Tally&, int, u32& lo, u32& hi, int t) const { em.apply(lo, hi, t); }
-};
 
 template <int K, int ROWS>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void step_rule_bounded(const u64* __restrict__ src, u64* __restrict__ dst,
@@ -49,20 +36,21 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void step_rule_bounded(const u
     }
 }
 
-const void* bounded_kernel_of(int k, u32 flags) {
+const void* bounded_kernel_of(Nbhd nbhd, int k, u32 flags) {
+    if (nbhd != Nbhd::Moore) return nbhd_bounded_kernel(nbhd, k, flags);
     return kernel_of(k, flags, [](auto K, auto ROWS) { return (const void*)step_rule_bounded<K(), ROWS()>; });
 }
 
 }  // namespace
 
-int rule_bounded_blocks_per_cu(int k, u32 flags) { return blocks_per_cu(bounded_kernel_of(k, flags)); }
+int rule_bounded_blocks_per_cu(int k, u32 flags, Nbhd nbhd) { return blocks_per_cu(bounded_kernel_of(nbhd, k, flags)); }
 
 void launch_step_rule_bounded(int k, const Rule& rule, const BoardEdges& edges, const u64* src, u64* dst,
                               const LaneDesc* plan, i64 n_waves, const StepParams& p, hipStream_t s) {
     if (p.flags & STEP_SEAM) throw Error("step_rule_bounded has no seam-reading variant (sub-tiles run the torus only)");
     check_rule_masks("step_rule_bounded", rule);
     check_place("step_rule_bounded", edges);
-    const void* f = bounded_kernel_of(k, p.flags);
+    const void* f = bounded_kernel_of(rule.nbhd, k, p.flags);
     if (!f) throw Error(strprintf("no bounded rule kernel instantiated for depth %d", k));
     launch_generic("bounded rule", f, rule, src, dst, plan, n_waves, p, s, tile_args(&edges, 0, p));
 }

@@ -30,23 +30,24 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void step_rule(const u64* __re
     w.run();
 }
 
-const void* rule_kernel_of(int k, u32 flags) {
+const void* rule_kernel_of(Nbhd nbhd, int k, u32 flags) {
+    if (nbhd != Nbhd::Moore) return nbhd_rule_kernel(nbhd, k, flags);
     return kernel_of(k, flags, [](auto K, auto ROWS) { return (const void*)step_rule<K(), ROWS()>; });
 }
 
 }  // namespace
 
-bool rule_depth_supported(int k) { return k >= 1 && k <= max_rule_depth(); }
+bool rule_depth_supported(int k, Nbhd nbhd) { return k >= 1 && k <= max_rule_depth(nbhd); }
 
-int max_rule_depth() { return kMaxRuleDepth; }
+int max_rule_depth(Nbhd) { return kMaxRuleDepth; }
 
-int rule_blocks_per_cu(int k, u32 flags) { return blocks_per_cu(rule_kernel_of(k, flags)); }
+int rule_blocks_per_cu(int k, u32 flags, Nbhd nbhd) { return blocks_per_cu(rule_kernel_of(nbhd, k, flags)); }
 
 void launch_step_rule(int k, const Rule& rule, const u64* src, u64* dst, const LaneDesc* plan, i64 n_waves,
                       const StepParams& p, hipStream_t s) {
     if (p.flags & STEP_SEAM) throw Error("step_rule has no seam-reading variant (sub-tiles run B3/S23 only)");
     check_rule_masks("step_rule", rule);
-    const void* f = rule_kernel_of(k, p.flags);
+    const void* f = rule_kernel_of(rule.nbhd, k, p.flags);
     if (!f) throw Error(strprintf("no rule kernel instantiated for depth %d", k));
     launch_generic("rule", f, rule, src, dst, plan, n_waves, p, s);
 }

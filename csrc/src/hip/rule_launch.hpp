@@ -10,13 +10,26 @@
 
 namespace gol {
 namespace hipk {
+
+// The von Neumann and hexagonal instantiations of the four kernels (nbhd_rule_kernel.hip, nbhd_bounded_kernel.hip,
+// nbhd_census_kernel.hip, nbhd_signature_kernel.hip; the gates: nbhd_gates.hpp), units of their own so that they
+// build beside the Moore units and leave those objects alone.  nullptr: depth k is not instantiated.
+const void* nbhd_rule_kernel(Nbhd nbhd, int k, u32 flags);
+const void* nbhd_bounded_kernel(Nbhd nbhd, int k, u32 flags);
+const void* nbhd_census_kernel(Nbhd nbhd, int k, u32 flags, bool bounded);
+const void* nbhd_signature_kernel(Nbhd nbhd, int k, u32 flags, bool bounded);
+
 namespace {
 
 constexpr int kMaxRuleDepth = 8;  // depths K = 1 .. 8 are instantiated: every remainder of a superstep is one pass
 
+// The masks within the neighbourhood's range of counts (8, von Neumann 4, hexagonal 6).
 inline void check_rule_masks(const char* kernel, const Rule& rule) {
-    if ((rule.birth & 1u) || rule.birth > 0x1FFu || rule.survive > 0x1FFu)
-        throw Error(strprintf("%s: rule masks outside B1..8 / S0..8 (B0 is out of scope)", kernel));
+    if ((unsigned)rule.nbhd > (unsigned)Nbhd::Hex) throw Error(strprintf("%s: unknown neighbourhood %u", kernel, (unsigned)rule.nbhd));
+    const int top = nbhd_max_count(rule.nbhd);
+    const u32 all = (2u << top) - 1u;
+    if ((rule.birth & 1u) || rule.birth > all || rule.survive > all)
+        throw Error(strprintf("%s: rule masks outside B1..%d / S0..%d (B0 is out of scope)", kernel, top, top));
 }
 
 inline void check_place(const char* kernel, const BoardEdges& e) {

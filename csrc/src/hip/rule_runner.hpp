@@ -56,6 +56,8 @@
 // row, wraps several times per pass on a 1-, 2- or 3-row board; i does not.)
 #pragma once
 
+#include <type_traits>
+
 #include "gol/bits.hpp"
 #include "gol/hip_kernels.hpp"
 #include "stencil_device.hpp"
@@ -227,12 +229,28 @@ struct CountTally {
     }
 };
 
+// hsum_split (stencil_device.hpp, step_temporal's: left as it is) that also hands out the two shifted words it
+// forms: Le, the left neighbours of the even cells, and Ro, the right neighbours of the odd cells.
+__device__ __forceinline__ void hsum_split_lr(u32 lo, u32 hi, u32& s0lo, u32& s1lo, u32& s0hi, u32& s1hi, u32& Le, u32& Ro) {
+    const u32 ph = dpp_prev(hi), nl = dpp_next(lo);
+    Le = __builtin_amdgcn_alignbit(hi, ph, 31);  // (hi << 1) | (ph >> 31)
+    Ro = __builtin_amdgcn_alignbit(nl, lo, 1);   // (lo >> 1) | (nl << 31)
+    s0lo = b3<kLutXor3>(Le, lo, hi);
+    s1lo = b3<kLutMaj>(Le, lo, hi);
+    s0hi = b3<kLutXor3>(lo, hi, Ro);
+    s1hi = b3<kLutMaj>(lo, hi, Ro);
+}
+
 // The streaming wave: one wave streams one plan segment through the K levels and stores its output rows.
-template <int K, int ROWS, class Policy>
+// Gates is the neighbourhood: RuleGates (Moore; the default, and the code of this header), or the von Neumann or
+// hexagonal gates of nbhd_gates.hpp, which finish a level from the same register ring (advance tells how).  The
+// Moore path stands inside `if constexpr` as it stood before there were other gates: its instantiations' gfx950
+// code is what it was (docs/PERFORMANCE.md section 24).
+template <int K, int ROWS, class Policy, class Gates = RuleGates>
 struct RuleRunner {
     static_assert(ROWS == ROWS_GHOST || ROWS == ROWS_WRAP, "the generic-rule kernels read ghost rows or wrap");
     static constexpr int D = prefetch_rows<K>();
-    const RuleGates step;
+    const Gates step;
     const StepParams& p;
     const LaneDesc& d;
     const int n;   // row iterations: nrows + 2K
@@ -258,7 +276,7 @@ struct RuleRunner {
 
     template <class... A>
     __device__ __forceinline__ RuleRunner(const u64* src, u64* dst, const LaneDesc& d_, int nrows, const StepParams& p_,
-                                          i64 wave_id, const RuleGates& step_, const A&... policy_args)
+                                          i64 wave_id, const Gates& step_, const A&... policy_args)
         : step(step_), p(p_), d(d_), n(nrows + 2 * K), hp((i64)p_.h * p_.pitch), policy(d_, nrows, p_, policy_args...) {
         lrow = d.row0 - K;
         if (ROWS == ROWS_WRAP && lrow < 0) lrow += p.h;
@@ -285,14 +303,25 @@ struct RuleRunner {
             const int s = (PH + l) % 3;   // slot of the arriving row
             const int sp = (s + 2) % 3;   // previous row (centre of the output)
             const int spp = (s + 1) % 3;  // two rows back
-            hsum_split(lo, hi, P.s0[l][s][0], P.s1[l][s][0], P.s0[l][s][1], P.s1[l][s][1]);
-            P.x[l][s][0] = lo;
-            P.x[l][s][1] = hi;
-            if (GUARD && i < 2 * l + 2) return false;
-            lo = step.rule(P.s0[l][spp][0], P.s1[l][spp][0], P.s0[l][sp][0], P.s1[l][sp][0], P.s0[l][s][0],
-                           P.s1[l][s][0], P.x[l][sp][0]);
-            hi = step.rule(P.s0[l][spp][1], P.s1[l][spp][1], P.s0[l][sp][1], P.s1[l][sp][1], P.s0[l][s][1],
-                           P.s1[l][s][1], P.x[l][sp][1]);
+            if constexpr (std::is_same<Gates, RuleGates>::value) {
+                hsum_split(lo, hi, P.s0[l][s][0], P.s1[l][s][0], P.s0[l][s][1], P.s1[l][s][1]);
+                P.x[l][s][0] = lo;
+                P.x[l][s][1] = hi;
+                if (GUARD && i < 2 * l + 2) return false;
+                lo = step.rule(P.s0[l][spp][0], P.s1[l][spp][0], P.s0[l][sp][0], P.s1[l][sp][0], P.s0[l][s][0],
+                               P.s1[l][s][0], P.x[l][sp][0]);
+                hi = step.rule(P.s0[l][spp][1], P.s1[l][spp][1], P.s0[l][sp][1], P.s1[l][sp][1], P.s0[l][s][1],
+                               P.s1[l][s][1], P.x[l][sp][1]);
+            } else {
+                // other neighbourhoods: the gates take the arriving row's shifted words too (used at once), and
+                // read the rows above and below the centre from the ring's x, not from their horizontal sums
+                u32 Le, Ro;
+                hsum_split_lr(lo, hi, P.s0[l][s][0], P.s1[l][s][0], P.s0[l][s][1], P.s1[l][s][1], Le, Ro);
+                P.x[l][s][0] = lo;
+                P.x[l][s][1] = hi;
+                if (GUARD && i < 2 * l + 2) return false;
+                step.next(P, l, s, sp, spp, Le, Ro, lo, hi);
+            }
             policy.level(tally, l, lo, hi, i - (l + 1));
         }
         return true;

@@ -44,93 +44,12 @@
 // Depths K = 1 .. 8, both row modes, both boundaries; registers: docs/PERFORMANCE.md section 22.
 #include "gol/signature.hpp"
 #include "rule_launch.hpp"
+#include "rule_policies.hpp"
 
 namespace gol {
 namespace hipk {
 
 namespace {
-
-template <int K, int MASK, bool BOUNDED>
-struct SigPolicy {
-    static constexpr int kRowBarriers = 2;
-    EdgeMask<MASK> em;  // BOUNDED
-    OwnMask<MASK> own;
-    u32 gam_e, gam_o;  // column keys of the lane's word
-    u32 growb;         // (u32) global row of row counter t = 0: grow0 + row0 - K
-    unsigned long long* const sig;  // LDS: level l's accumulator of this lane at sig[l * block size]
-    using Tally = CountTally<K>;
-
-    __device__ __forceinline__ SigPolicy(const LaneDesc& d, int nrows, const StepParams& p, const TileArgs& ta,
-                                         unsigned long long* lds)
-        : sig(lds + threadIdx.x) {
-        const bool stores = d.flags & LANE_STORE;  // (ahead of the masks: the prologue's order, PERFORMANCE.md section 23)
-        if (BOUNDED) em.template init<K>(d, ta);
-        own.template init<K>(stores, d, nrows, p, ta);
-        // the keys: the lane's two column keys, and the global row of row counter 0
-        const u32 gw2 = 2u * (u32)(ta.gword0 + d.col);
-        gam_e = sig_gam(gw2);
-        gam_o = sig_gam(gw2 + 1u);
-        const int gb = (int)(u32)(ta.grow0 + (i64)d.row0 - K);
-        growb = (u32)(MASK == MASK_UNI ? __builtin_amdgcn_readfirstlane(gb) : gb);
-#pragma unroll
-        for (int l = 0; l < K; ++l) sig[l * (64 * kWavesPerBlock)] = 0;
-    }
-
-    // The key of the global row of row counter t, a value of its own at every use (the header tells why).
-    __device__ __forceinline__ u32 row_key(int t) const {
-        if (MASK == MASK_UNI) {
-            u32 r = sig_rho(growb + (u32)t);
-            asm volatile("" : "+s"(r));
-            return r;
-        }
-        asm volatile("" : "+s"(t));
-        return sig_rho(growb + (u32)t);
-    }
-
-    // (BOUNDED) the loaded row: ghost rows and words hold the torus neighbour's cells
-    __device__ __forceinline__ void input(u32& lo, u32& hi, int i) const {
-        if (BOUNDED) em.apply(lo, hi, i);
-    }
-    // the (masked) output of level l is counted into acc[l] and hashed into the lane's LDS slot of level l
-    __device__ __forceinline__ void level(Tally& ty, int l, u32& lo, u32& hi, int t) const {
-        if (BOUNDED) em.apply(lo, hi, t);
-        const u32 rho = row_key(t);
-        const u32 r = own.row(t);
-        const u32 o = b3<kLutAnd3>(hi, own.own_hi, r);
-        const u32 e = b3<kLutAnd3>(lo, own.own_lo, r);
-        ty.acc[l] = (u32)__builtin_popcount(o) + ty.acc[l];
-        ty.acc[l] = (u32)__builtin_popcount(e) + ty.acc[l];
-        const u64 p = (u64)e * (u64)(rho * gam_e) + (u64)o * (u64)(rho * gam_o);
-        atomicAdd(sig + l * (64 * kWavesPerBlock), (unsigned long long)p);  // (the lane's own slot: a ds_add_u64 without return)
-    }
-    // The wave's count and signature of each level: summed over the lanes, two 64-bit atomics per level from lane 0.
-    __device__ __forceinline__ void finish(const Tally& ty, i64 wave_id, u64* slots) const {
-        if (!slots) return;
-        const size_t stripe = (size_t)(wave_id & (kSigStripes - 1)) * kSigStripeWords;
-#pragma unroll
-        for (int l = 0; l < K; ++l) {
-            u32 v = ty.acc[l];
-            const unsigned long long sl = sig[l * (64 * kWavesPerBlock)];
-            u32 s_lo = (u32)sl, s_hi = (u32)(sl >> 32);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                v += __shfl_xor(v, off, 64);
-                // 64-bit wrapping add over the lanes, in halves with the carry
-                const u32 o_lo = __shfl_xor(s_lo, off, 64), o_hi = __shfl_xor(s_hi, off, 64);
-                const u32 n_lo = s_lo + o_lo;
-                s_hi = s_hi + o_hi + (n_lo < s_lo ? 1u : 0u);
-                s_lo = n_lo;
-            }
-            if ((threadIdx.x & 63) == 0 && v != 0) {
-                // (no live owned cell: the signature's share is 0 too)
-                u64* slot = slots + (size_t)l * kSigSlotWords + stripe;
-                atomicAdd(reinterpret_cast<unsigned long long*>(slot), (unsigned long long)v);
-                atomicAdd(reinterpret_cast<unsigned long long*>(slot + kSigSigOffset),
-                          ((unsigned long long)s_hi << 32) | (unsigned long long)s_lo);
-            }
-        }
-    }
-};
 
 template <int K, int ROWS, bool BOUNDED>
 // (the second launch bound: at least two waves per SIMD, so at most 256 registers and none of them an AGPR copy)
@@ -155,7 +74,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock, 2) void step_signature(const u
     }
 }
 
-const void* signature_kernel_of(int k, u32 flags, bool bounded) {
+const void* signature_kernel_of(Nbhd nbhd, int k, u32 flags, bool bounded) {
+    if (nbhd != Nbhd::Moore) return nbhd_signature_kernel(nbhd, k, flags, bounded);
     return kernel_of(k, flags, [bounded](auto K, auto ROWS) {
         return bounded ? (const void*)step_signature<K(), ROWS(), true> : (const void*)step_signature<K(), ROWS(), false>;
     });
@@ -205,9 +125,11 @@ unsigned reduce_grid(i64 n) {
 
 }  // namespace
 
-int max_signature_depth() { return kMaxRuleDepth; }
+int max_signature_depth(Nbhd) { return kMaxRuleDepth; }
 
-int signature_blocks_per_cu(int k, u32 flags, bool bounded) { return blocks_per_cu(signature_kernel_of(k, flags, bounded)); }
+int signature_blocks_per_cu(int k, u32 flags, bool bounded, Nbhd nbhd) {
+    return blocks_per_cu(signature_kernel_of(nbhd, k, flags, bounded));
+}
 
 void launch_step_signature(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src,
                            u64* dst, const LaneDesc* plan, i64 n_waves, const StepParams& p, u64* slots, hipStream_t s) {
@@ -215,7 +137,7 @@ void launch_step_signature(int k, const Rule& rule, const BoardEdges& place, boo
     check_rule_masks("step_signature", rule);
     check_place("step_signature", place);
     check_tile_cols("step_signature", tile_cols, p);
-    const void* f = signature_kernel_of(k, p.flags, bounded);
+    const void* f = signature_kernel_of(rule.nbhd, k, p.flags, bounded);
     if (!f) throw Error(strprintf("no signature kernel instantiated for depth %d (1..%d)", k, kMaxRuleDepth));
     launch_generic("signature", f, rule, src, dst, plan, n_waves, p, s, tile_args(&place, tile_cols, p), slots);
 }

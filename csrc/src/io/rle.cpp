@@ -78,10 +78,13 @@ std::string canonical_rule(const std::string& r) {
     std::string s = r;
     const size_t slash = r.find('/');
     if (slash != std::string::npos) {
-        bool digits = r.size() > 1;
-        for (size_t k = 0; k < r.size(); ++k)
+        // the neighbourhood suffix (V, H) follows the second list in this form too: 34/2H
+        const char last = (char)std::toupper((unsigned char)r.back());
+        const size_t end = (last == 'V' || last == 'H') && r.size() - 1 > slash ? r.size() - 1 : r.size();
+        bool digits = end > 1;
+        for (size_t k = 0; k < end; ++k)
             if (k != slash && !std::isdigit((unsigned char)r[k])) digits = false;
-        if (digits) s = "B" + r.substr(slash + 1) + "/S" + r.substr(0, slash);
+        if (digits) s = "B" + r.substr(slash + 1, end - slash - 1) + "/S" + r.substr(0, slash) + r.substr(end);
     }
     try {
         return Rule::parse(s).str();

@@ -321,7 +321,7 @@ void save_checkpoint(Engine& eng, const std::string& prefix, u64 seed) {
         hd.words_per_row = (u64)gw;
         hd.generation = eng.generation();
         hd.seed = seed;
-        hd.reserved[0] = eng.config().rule.code();  // birth | survive << 16 (0, older files: B3/S23)
+        hd.reserved[0] = eng.config().rule.code();  // birth | neighbourhood << 12 | survive << 16 (0, older files: B3/S23)
         hd.reserved[1] = (u64)eng.config().boundary;  // 0 torus (and every older file), 1 dead
         const int fd = open(tmp.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
         ok = fd >= 0 && ftruncate(fd, (off_t)(sizeof(hd) + (size_t)(g.dec.H * gw) * 8)) == 0 &&
@@ -382,7 +382,8 @@ u64 load_checkpoint(Engine& eng, const std::string& prefix) {
         const Rule mine = eng.config().rule;
         const u64 code = hd.reserved[0] ? hd.reserved[0] : Rule().code();
         if (code != mine.code()) {
-            const Rule theirs = Rule::from_masks((unsigned)(code & 0xFFFFu), (unsigned)((code >> 16) & 0xFFFFu));
+            if (code >> 32) throw Error("checkpoint " + name + " names an unknown rule");
+            const Rule theirs = Rule::from_code((u32)code);
             throw Error("checkpoint " + name + " was written under rule " + theirs.str() + ", this run has " +
                         mine.str());
         }

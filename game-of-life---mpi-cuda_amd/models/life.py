@@ -47,7 +47,9 @@ class Simulation:
                   self-exchange) and for ranks that can run two sub-tiles, 56 for 2-D tiles of >= 2048
                   rows with neighbours, otherwise 32).
     rule:         the life-like rule, ``"B36/S23"`` or an alias (conway, life, highlife, daynight, seeds,
-                  replicator); default B3/S23 (GOL_RULE).  B3/S23 runs the specialised bit-sliced kernels;
+                  replicator); default B3/S23 (GOL_RULE).  A ``V`` or ``H`` directly after the second list counts the
+                  von Neumann (N, S, W, E; digits 0..4) or hexagonal (N, S, W, E, NW, SE; digits 0..6) neighbourhood
+                  instead of Moore's eight: ``"B13/S13V"``, ``"B2/S34H"``.  B3/S23 runs the specialised bit-sliced kernels;
                   any other B0-free rule the generic ones (HIP: ``step_rule``, CPU: a bit-sliced count),
                   without ``compat``, ``subtiles=2`` or the B3/S23-only kernels.
     kernel_depth: generations per kernel pass (HIP; 0 = auto).  A superstep of halo_depth

@@ -10,6 +10,7 @@ from .oracle import (  # noqa: F401
     numpy_step_rule,
     numpy_step_rule_bounded,
     parse_rule,
+    parse_rule_nbhd,
     quirk_model,
     random_board,
     rule_string,

@@ -59,50 +59,83 @@ _RULE_ALIASES = {
 }
 
 
-def parse_rule(rule) -> tuple:
-    """A rule as ``(birth, survive)`` masks: bit c of birth / survive = a dead / live cell with c live
-    neighbours is alive next generation.  Takes ``"B36/S23"`` (either order, either case, empty digit
-    lists allowed), an alias (conway, life, highlife, daynight, seeds, replicator) or a mask pair.
-    B0 rules are refused, as in the engine."""
+# The neighbours a rule counts, by its suffix, as 3 x 3 masks around the centre (rows downward, columns rightward):
+# Moore (no suffix), von Neumann (V), hexagonal (H: the square-grid emulation without the NE and SW corners).
+NEIGHBOURHOODS = {
+    "": ((1, 1, 1), (1, 0, 1), (1, 1, 1)),
+    "V": ((0, 1, 0), (1, 0, 1), (0, 1, 0)),
+    "H": ((1, 1, 0), (1, 0, 1), (0, 1, 1)),
+}
+
+
+def parse_rule_nbhd(rule) -> tuple:
+    """A rule as ``(birth, survive, nbhd)``: the masks of :func:`parse_rule` and the neighbourhood's suffix, ``""``
+    (Moore), ``"V"`` (von Neumann) or ``"H"`` (hexagonal), a key of :data:`NEIGHBOURHOODS`.  Takes what
+    :func:`parse_rule` takes, a rule string with the suffix directly after the second list (``"B2/S34H"``, either
+    case), or a ``(birth, survive, nbhd)`` triple.  Digits beyond the neighbourhood's largest count (8, V: 4, H: 6)
+    are refused, and B0 rules, as in the engine."""
+    nbhd = ""
     if not isinstance(rule, str):
-        birth, survive = (int(v) for v in rule)
-        if not (0 <= birth < 512 and 0 <= survive < 512):
-            raise ValueError(f"invalid rule {rule!r}: masks have bits 0..8")
+        vals = tuple(rule)
+        if len(vals) == 3:
+            nbhd = str(vals[2]).upper()
+            if nbhd not in NEIGHBOURHOODS:
+                raise ValueError(f"invalid rule {rule!r}: the neighbourhood is '', 'V' or 'H'")
+            vals = vals[:2]
+        birth, survive = (int(v) for v in vals)
+        top = sum(sum(row) for row in NEIGHBOURHOODS[nbhd])
+        if not (0 <= birth < (2 << top) and 0 <= survive < (2 << top)):
+            raise ValueError(f"invalid rule {rule!r}: masks have bits 0..{top}")
     else:
         text = _RULE_ALIASES.get(rule.lower(), rule.lower())
+        if text[-1:] in ("v", "h"):  # directly after the second list
+            nbhd, text = text[-1].upper(), text[:-1]
         parts = text.split("/")
         if len(parts) != 2 or {p[:1] for p in parts} != {"b", "s"}:
             raise ValueError(f"invalid rule {rule!r}: expected B<digits>/S<digits>")
+        top = sum(sum(row) for row in NEIGHBOURHOODS[nbhd])
         masks = {}
         for p in parts:
             digits = p[1:]
-            if not all(c in "012345678" for c in digits) or len(set(digits)) != len(digits):
-                raise ValueError(f"invalid rule {rule!r}: digits are 0..8, each at most once")
+            if not all(c in "012345678"[: top + 1] for c in digits) or len(set(digits)) != len(digits):
+                raise ValueError(f"invalid rule {rule!r}: digits are 0..{top}, each at most once")
             masks[p[0]] = sum(1 << int(c) for c in digits)
         birth, survive = masks["b"], masks["s"]
     if birth & 1:
         raise ValueError(f"invalid rule {rule!r}: B0 rules are out of scope (the dead background would come alive)")
-    return birth, survive
+    return birth, survive, nbhd
+
+
+def parse_rule(rule) -> tuple:
+    """A rule as ``(birth, survive)`` masks: bit c of birth / survive = a dead / live cell with c live
+    neighbours is alive next generation.  Takes ``"B36/S23"`` (either order, either case, empty digit
+    lists allowed), an alias (conway, life, highlife, daynight, seeds, replicator) or a mask pair.
+    B0 rules are refused, as in the engine.  A neighbourhood suffix (``"B2/S34H"``) is accepted and not returned:
+    :func:`parse_rule_nbhd` returns it."""
+    return parse_rule_nbhd(rule)[:2]
 
 
 def rule_string(rule) -> str:
-    """Canonical ``B<digits>/S<digits>`` (digits ascending)."""
-    birth, survive = parse_rule(rule)
+    """Canonical ``B<digits>/S<digits>`` (digits ascending), then the neighbourhood's ``V`` or ``H``."""
+    birth, survive, nbhd = parse_rule_nbhd(rule)
     digits = lambda m: "".join(str(c) for c in range(9) if (m >> c) & 1)  # noqa: E731
-    return f"B{digits(birth)}/S{digits(survive)}"
+    return f"B{digits(birth)}/S{digits(survive)}{nbhd}"
 
 
 def numpy_step_rule(board: np.ndarray, rule, generations: int = 1) -> np.ndarray:
-    """Byte-per-cell torus step of a life-like rule (string or ``(birth, survive)`` pair)."""
-    birth, survive = parse_rule(rule)
+    """Byte-per-cell torus step of a life-like rule (string, ``(birth, survive)`` pair or ``(birth, survive, nbhd)``
+    triple): shifted adds over the rule's neighbourhood mask (:data:`NEIGHBOURHOODS`)."""
+    birth, survive, nbhd = parse_rule_nbhd(rule)
+    mask = NEIGHBOURHOODS[nbhd]
     lut = np.array([[(birth >> c) & 1 for c in range(9)], [(survive >> c) & 1 for c in range(9)]], dtype=np.uint8)
     b = np.asarray(board, dtype=np.uint8)
     for _ in range(generations):
+        # the neighbour at (row + dy, column + dx) comes to the cell by a roll of (-dy, -dx)
         n = sum(
-            np.roll(np.roll(b, dy, axis=0), dx, axis=1)
+            np.roll(np.roll(b, -dy, axis=0), -dx, axis=1)
             for dy in (-1, 0, 1)
             for dx in (-1, 0, 1)
-            if dy or dx
+            if mask[dy + 1][dx + 1]
         )
         b = lut[b, n]
     return b
@@ -111,7 +144,8 @@ def numpy_step_rule(board: np.ndarray, rule, generations: int = 1) -> np.ndarray
 def numpy_step_rule_bounded(board: np.ndarray, rule, generations: int = 1) -> np.ndarray:
     """Byte-per-cell step of a life-like rule on a bounded board: every cell outside the array is dead in every
     generation.  Written on its own, from a neighbour count over a zero-padded copy (no roll, no torus oracle)."""
-    birth, survive = parse_rule(rule)
+    birth, survive, nbhd = parse_rule_nbhd(rule)
+    mask = NEIGHBOURHOODS[nbhd]
     b = np.asarray(board, dtype=np.uint8)
     if b.ndim != 2:
         raise ValueError(f"a board is a 2-D array, got shape {b.shape}")
@@ -122,7 +156,7 @@ def numpy_step_rule_bounded(board: np.ndarray, rule, generations: int = 1) -> np
         n = np.zeros((H, W), dtype=np.int32)
         for dy in (0, 1, 2):
             for dx in (0, 1, 2):
-                if dy != 1 or dx != 1:
+                if mask[dy][dx]:  # (pad is shifted by one: mask[dy][dx] is the neighbour at (row + dy - 1, column + dx - 1))
                     n += pad[dy : dy + H, dx : dx + W]
         alive = b == 1
         b = np.where(alive, (survive >> n) & 1, (birth >> n) & 1).astype(np.uint8)
@@ -193,13 +227,13 @@ def torch_step_rule(board, rule, generations: int = 1, device=None):
     import torch
     import torch.nn.functional as F
 
-    birth, survive = parse_rule(rule)
+    birth, survive, nbhd = parse_rule_nbhd(rule)
     if isinstance(board, torch.Tensor):
         x = board.to(device=device if device is not None else board.device, dtype=torch.float32)[None, None]
     else:
         x = torch.as_tensor(np.asarray(board), dtype=torch.float32, device=device)[None, None]
-    k = torch.ones(1, 1, 3, 3, dtype=torch.float32, device=x.device)
-    k[0, 0, 1, 1] = 0
+    # (conv2d is a cross-correlation: the kernel is the neighbourhood mask as it stands)
+    k = torch.tensor(NEIGHBOURHOODS[nbhd], dtype=torch.float32, device=x.device)[None, None]
     lut = torch.tensor(
         [(birth >> c) & 1 for c in range(9)] + [(survive >> c) & 1 for c in range(9)], dtype=torch.float32, device=x.device
     )

@@ -15,9 +15,9 @@ def pattern_from_cells(cells, rule: str = "", topology: str = "", bound_cols: in
     if cells.ndim != 2 or cells.shape[0] < 1 or cells.shape[1] < 1:
         raise ValueError(f"a pattern is a 2-D array with at least one cell, got shape {cells.shape}")
     if rule:
-        from .oracle import parse_rule, rule_string
+        from .oracle import rule_string
 
-        rule = rule_string(parse_rule(rule))
+        rule = rule_string(rule)
     return _gol.RlePattern(pack_cells(cells != 0), int(cells.shape[1]), rule, topology, int(bound_cols), int(bound_rows))
 
 
