@@ -203,6 +203,16 @@ PYBIND11_MODULE(_gol, m) {
         for (auto& t : regions) rg.push_back({std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t)});
         return choose_rows_per_chunk(rg, k, target, min_rows);
     });
+    m.def(
+        "balanced_rows_per_chunk",
+        [](const std::vector<std::tuple<i64, i64, i64, i64>>& regions, i64 nw, i64 h, int k, i64 resident_waves,
+           i64 min_rows, bool xwrap) {
+            std::vector<Region> rg;
+            for (auto& t : regions) rg.push_back({std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t)});
+            return balanced_rows_per_chunk(rg, nw, h, k, resident_waves, min_rows, xwrap);
+        },
+        py::arg("regions"), py::arg("nw"), py::arg("h"), py::arg("k"), py::arg("resident_waves"), py::arg("min_rows"),
+        py::arg("xwrap") = false);
 
     // ---- transports -----------------------------------------------------------------------
     py::class_<Transport, std::shared_ptr<Transport>>(m, "Transport")

@@ -507,6 +507,28 @@ void HipEngine::finish_init() {
             }
             tn += strprintf("%scut%d=%s", tn.empty() ? "" : " ", k, c.c_str());
         }
+    // sub-tile mode: the halves' cut and, per half and pass, the prepared plan's rows per segment and waves
+    // (sub<k>.<half>.<pass>, or <first>-<last> for consecutive passes of one depth with equal plans; the plans
+    // prepare_dual builds below)
+    if (dual_)
+        for (int k : init_depths()) {
+            std::string c, sp;
+            const std::vector<int>& ps = pass_depths(k);
+            prepare_dual(k);  // (builds the plans in the order it always has; read here)
+            for (size_t j = 0; j < ps.size(); ++j) c += (j ? "+" : "") + strprintf("temporal@%d", ps[j]);
+            for (int s = 0; s < 2; ++s)
+                for (size_t j = 0, j1; j < ps.size(); j = j1 + 1) {
+                    const DevPlan& pl = sub_plan(s, ps[j], ext_after(ps, j));
+                    for (j1 = j; j1 + 1 < ps.size() && ps[j1 + 1] == ps[j]; ++j1) {
+                        const DevPlan& nx = sub_plan(s, ps[j1 + 1], ext_after(ps, j1 + 1));
+                        if (nx.rows != pl.rows || nx.waves != pl.waves) break;
+                    }
+                    sp += strprintf(" sub%d.%d.%d", k, s, (int)j);
+                    if (j1 > j) sp += strprintf("-%d", (int)j1);
+                    sp += strprintf("=%lldrows,%lldwaves", (long long)pl.rows, (long long)pl.waves);
+                }
+            tn += strprintf("%scut%d=%s%s", tn.empty() ? "" : " ", k, c.c_str(), sp.c_str());
+        }
     if (!split_ && !dual_ && !res_ && tile_kernel(0) && kernel_ != "lds") {  // the tile variant the full superstep runs
         const DevPlan& p0 = plan(0, kdepth_, 0);
         tn += strprintf("%stile_plan=%s,%lldrows,%lldtiles", tn.empty() ? "" : " ",

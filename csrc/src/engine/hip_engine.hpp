@@ -195,7 +195,9 @@ class HipEngine : public Engine {
     // halves, and memory for one more board pair.  (The halves always run the temporal kernel, at
     // its own pass depth, whatever the one-tile kernel autotune picked.)
     bool dual_local_ok() const {
-        if (L_.h < 8 * (i64)L_.R) return false;
+        // setup_dual cuts a tile shorter than 16 R into halves of 8 R and h - 8 R rows; each half must hold the R
+        // edge rows the other one's seam pass (and the exchange) reads, or those reads reach its ghost rows
+        if (L_.h < 9 * (i64)L_.R) return false;
         size_t fr = 0, tot = 0;
         if (hipMemGetInfo(&fr, &tot) != hipSuccess) return false;
         return 3 * alloc_bytes_ + ((size_t)1 << 30) < fr;  // 3 buffers of half a tile per half

@@ -217,8 +217,10 @@ def test_naive_yardstick(gol):
 @pytest.mark.parametrize("depth", [6, 7, 12])
 def test_pingpong_loop_depths(gol, depth):
     """Depths that run the two-triple steady loop (K = 6, 7, 12), with tall segments (300 rows) so the
-    loop runs many six-row iterations plus its leftover triple and tail rows, on the torus and with
-    ghost rows (two passes per superstep)."""
+    loop runs many six-row iterations, in supersteps of one pass and of two.  One rank is its own N / S
+    neighbour, so both passes are periodic-row passes (ROWS_WRAP) and 300 rows are one residue of the row
+    iterations mod 6; the loop with ghost rows (ROWS_GHOST, K = 5 too) and every loop tail are in
+    test_gpu_temporal.py (test_ghost_loop_tails, test_wrap_loop_tails)."""
     N = 2048
     for R, gens in ((depth, 3 * depth + 1), (2 * depth, 2 * depth + 5)):
         s = _sim(gol, N, halo_depth=R, kernel_depth=depth, kernel="temporal", rows_per_wave=300, subtiles=0)

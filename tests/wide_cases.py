@@ -132,13 +132,15 @@ def xwrap(W, boundary):
     return W % 64 == 0 and boundary == "torus"
 
 
-def build(gol, H, W, K, boundary="torus", rows_per_wave=0, region=None):
+def build(gol, H, W, K, boundary="torus", rows_per_wave=0, region=None, x_wrap=None):
     """The plan of a pass of depth K over ``region`` (default: the whole tile, rows [0, H) x words [0, nw)) as the
-    engine builds it: ``(waves, stats)``, the waves with nrows > 0 only; ``stats["waves"]`` counts the padding too."""
+    engine builds it: ``(waves, stats)``, the waves with nrows > 0 only; ``stats["waves"]`` counts the padding too.
+    ``x_wrap``: the plan's x-wrap when it is not ``xwrap(W, boundary)`` (False on a rank with x neighbours)."""
     nw = nwords(W)
     region = region if region is not None else (0, H, 0, nw)
     rows = engine_rows(region[1] - region[0], K, rows_per_wave)
-    lanes, stats = gol.native.build_plan([tuple(int(v) for v in region)], nw, H, rows, K, xwrap(W, boundary), False)
+    x_wrap = xwrap(W, boundary) if x_wrap is None else x_wrap
+    lanes, stats = gol.native.build_plan([tuple(int(v) for v in region)], nw, H, rows, K, x_wrap, False)
     lanes = np.asarray(lanes).reshape(-1, LANES, 4)
     assert stats["waves"] == lanes.shape[0]
     waves = []
@@ -272,7 +274,7 @@ Part = collections.namedtuple("Part", "rank row0 col0 board stats result")
 RANK_GENS, RANK_HALO, RANK_KDEPTH = 40, 16, 8
 
 
-def run_ranks(gol, P, H, W, backend, script=None, **kw):
+def run_ranks(gol, P, H, W, backend, script=None, halo_depth=RANK_HALO, kernel_depth=RANK_KDEPTH, **kw):
     """A global H x W board on P thread ranks, one daemon thread each, joined within JOIN_S seconds: ``script(sim)``
     (default: RANK_GENS generations) runs after ``init(5, seed=SEED)``.  A rank that raises fails the test with its
     message; nothing is retried.  ``stats`` is taken after init."""
@@ -286,8 +288,8 @@ def run_ranks(gol, P, H, W, backend, script=None, **kw):
 
     def rank_main(r):
         try:
-            s = gol.Simulation(H, ts[r], backend=backend, global_mode=True, width=W, halo_depth=RANK_HALO,
-                               kernel_depth=RANK_KDEPTH, **kw)
+            s = gol.Simulation(H, ts[r], backend=backend, global_mode=True, width=W, halo_depth=halo_depth,
+                               kernel_depth=kernel_depth, **kw)
             s.init(5, seed=SEED)
             stats = s.stats()
             result = None
@@ -325,15 +327,15 @@ def census_script(s):
     return start, series, s.population()
 
 
-def check_ranks(H, W, parts, ref, bands):
+def check_ranks(H, W, parts, ref, bands, K=RANK_KDEPTH):
     """The assembled board is ``ref``; the failure message is the report of the first wrong rank's tile, in its own
-    rows and words (``bands``: the rank plans' row bands in tile rows)."""
+    rows and words (``bands``: the rank plans' row bands in tile rows; ``K``: the pass depth)."""
     got = assemble(H, W, parts)
     if np.array_equal(got, ref):
         return got
     for p in parts:
         h, w = p.board.shape
-        rep = mismatch_report(p.board, ref[p.row0 : p.row0 + h, p.col0 : p.col0 + w], RANK_KDEPTH, bands)
+        rep = mismatch_report(p.board, ref[p.row0 : p.row0 + h, p.col0 : p.col0 + w], K, bands)
         if rep:
             raise AssertionError(f"rank {p.rank} (rows {p.row0}.., columns {p.col0}..):\n{rep}")
     raise AssertionError("cells that no rank owns")
