@@ -529,12 +529,21 @@ void HipEngine::finish_init() {
                 }
             tn += strprintf("%scut%d=%s%s", tn.empty() ? "" : " ", k, c.c_str(), sp.c_str());
         }
-    if (!split_ && !dual_ && !res_ && tile_kernel(0) && kernel_ != "lds") {  // the tile variant the full superstep runs
-        const DevPlan& p0 = plan(0, kdepth_, 0);
-        tn += strprintf("%stile_plan=%s,%lldrows,%lldtiles", tn.empty() ? "" : " ",
+    // the tile variant that runs: buffers, rows per tile, tiles, generations per LDS pass
+    auto tile_entry = [&](const char* name, const DevPlan& p0) {
+        tn += strprintf("%s%s=%s,%lldrows,%lldtiles,lv%d", tn.empty() ? "" : " ", name,
                         p0.fold ? ((p0.tflags & hipk::STEP_TILE_INPLACE) ? "fold-inplace" : "fold")
                                 : ((p0.tflags & hipk::STEP_TILE_INPLACE) ? "inplace" : "double"),
-                        (long long)p0.rows, (long long)p0.waves);
+                        (long long)p0.rows, (long long)p0.waves,
+                        (p0.tflags & hipk::STEP_TILE_L4) ? 4 : ((p0.tflags & hipk::STEP_TILE_L2) ? 2 : 1));
+    };
+    if (!split_ && !dual_ && !res_ && tile_kernel(0) && kernel_ != "lds")  // the full superstep's
+        tile_entry("tile_plan", plan(0, kdepth_, 0));
+    if (split_ && !dual_ && !res_ && !rule_ && kernel_ != "lds") {  // split: the interior's and the bands' of the first pass
+        const std::vector<int>& ps = pass_depths(L_.R);
+        const i64 e = ext_after(ps, 0);
+        if (tile_pass(1, ps[0]) && !regions(1, ps[0], e).empty()) tile_entry("tile_plan1", plan(1, ps[0], e));
+        if (tile_pass(2, ps[0]) && !regions(2, ps[0], e).empty()) tile_entry("tile_plan2", plan(2, ps[0], e));
     }
     stats_.tuning = tn + confirm_note_;
     stats_.registered = stats_registered_;
