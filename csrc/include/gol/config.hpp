@@ -57,7 +57,10 @@ struct Options {
     std::string census_out = "";    // GOL_CENSUS_OUT  implies it; rank 0 writes "generation,population" lines there
     bool signature = false;         // GOL_SIGNATURE signature mode: the board signature and population of every generation
     std::string signature_out = ""; // GOL_SIGNATURE_OUT  implies it; rank 0 writes "generation,population,signature" lines
-    std::string rle_out = "";       // GOL_RLE_OUT   rank 0 writes the final global board as RLE (<= 2^26 cells)
+    std::string film = "";          // GOL_FILM=r0,c0,rows,cols  film mode: that window of the board in every generation of the run
+    std::string film_out = "";      // GOL_FILM_OUT  needs GOL_FILM; rank 0 writes the frames there as a NumPy .npy file (uint8,
+                                    // shape (iterations, rows, cols))
+    std::string rle_out = "";       // GOL_RLE_OUT  rank 0 writes the final global board as RLE (<= 2^26 cells)
     std::string rule = "";          // the run's rule when GOL_PATTERN_FILE names one and GOL_RULE is unset
     std::string boundary = "";      // the run's boundary when GOL_PATTERN_FILE names a topology and GOL_BOUNDARY is
                                     // unset (GOL_BOUNDARY torus | dead is read beside GOL_RULE, runtime.cpp)

@@ -7,6 +7,7 @@
 // generation) so no exchange is needed inside the superstep.
 #pragma once
 
+#include "gol/film.hpp"
 #include "gol/geometry.hpp"
 #include "gol/pattern.hpp"
 #include "gol/rule.hpp"
@@ -48,8 +49,15 @@ void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, co
 // sigs (signature mode; k slots, or null): sigs[g] += the tile's share of the board signature (gol/signature.hpp)
 // after generation g + 1, over the same cells, keyed by edges.row0 and edges.word0 (the tile's place; needed on the
 // torus too).
+// film (film mode; frames == nullptr: none): frames + g * geo->slot_words() is the packed frame (gol/film.hpp) after
+// generation g + 1: the tile's own words (the same cells) that are words of the window are OR-ed into their place,
+// found from edges.row0 and edges.word0; the words of other tiles are left as they are.
+struct FilmOut {
+    const FilmGeo* geo = nullptr;
+    u64* frames = nullptr;  // k frames
+};
 u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule = Rule(), const Edges& edges = Edges(),
-               u64* counts = nullptr, u64* sigs = nullptr);
+               u64* counts = nullptr, u64* sigs = nullptr, const FilmOut& film = FilmOut());
 
 // x-periodic ghost words (and tail ghost bits) for rows [r_lo, r_hi).
 void fill_ghost_cols_wrap(u64* buf, const Layout& L, i64 r_lo, i64 r_hi);

@@ -23,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "gol/film.hpp"
 #include "gol/geometry.hpp"
 #include "gol/pattern.hpp"
 #include "gol/plan.hpp"
@@ -65,6 +66,10 @@ struct EngineConfig {
                                       // the board signature (gol/signature.hpp) and the population of that
                                       // generation (Engine::signatures).  HIP: step_signature runs every pass.
                                       // Not together with census (signature mode records the population too)
+    FilmRect film;                    // film mode (GOL_FILM=r0,c0,rows,cols): every generation run() computes also yields
+                                      // the cells of that window of the global board, window()'s coordinates and checks
+                                      // (Engine::film).  HIP: step_film stores them inside every pass.  Not together with
+                                      // census or signature
     int tile_waves = 8;               // tile kernel: waves per workgroup (4, 8, 16)
     bool tune_tile_waves = true;      // GOL_KERNEL=auto may also try 8 waves (false: GOL_TILE_WAVES set)
     std::string transport = "auto";   // auto | device | host  (host = stage halos through host memory)
@@ -115,6 +120,7 @@ struct EngineStats {
     std::string boundary;      // torus | dead
     bool census = false;       // census mode
     bool signature = false;    // signature mode
+    FilmRect film;             // film mode: the window (on = false: off)
     std::string schedule;      // superstep schedule: local (no neighbours) | split | full
     std::string tuning;        // init-time measurements behind the auto choices (HIP)
     bool registered = false;   // HIP + RCCL: the boards are registered with the communicator (zero-copy halos)
@@ -175,7 +181,28 @@ class Engine {
     // differ between the current board and the snapshot; throws, before any communication, without a snapshot.
     void snapshot();
     u64 snapshot_diff();
-    bool recording() const { return cfg_.census || cfg_.signature; }  // run() keeps a per-generation record
+    bool recording() const { return cfg_.census || cfg_.signature || cfg_.film.on; }  // run() keeps a per-generation record
+
+    // ----- film (EngineConfig::film) -----
+    // Collective: (start, n, frames): frame i, rows x cols 0/1 bytes at frames[i * rows * cols], is what
+    // window(r0, c0, rows, cols) would return at generation start + 1 + i, for every generation run() has computed
+    // since the record was cleared; the start, clear and restart rules are the census's (census_restart serves this
+    // mode too).  The same on every rank: each rank records the words of the window it owns (gol/film.hpp), the ranks'
+    // packed frames are summed over the control plane (disjoint bits) and unpacked on the host.  Throws, before any
+    // communication, on an engine that is not in film mode.
+    struct Film {
+        u64 start = 0;
+        size_t n = 0;
+        std::vector<u8> frames;
+    };
+    Film film();
+    void film_clear();
+    // film() in two steps, for a caller that owns the bytes: film_frames() brings this rank's record to the host and
+    // returns its frames (the same number on every rank; no communication); film_into() is the collective part and
+    // unpacks them into out (n * rows * cols bytes, n as returned), several rows at a time; it returns start.
+    size_t film_frames();
+    u64 film_into(u8* out, size_t n);
+    const FilmGeo& film_geo() const { return film_geo_; }
 
     // ----- views and pattern stamping -----
     // Global board coordinates on the torus: a window or a pattern may start anywhere (r0, c0 are taken
@@ -314,6 +341,8 @@ class Engine {
     virtual void census_collect() {}
     virtual void census_discard() {}
     std::vector<u64> census_host_, sig_host_;
+    std::vector<u64> film_host_;  // film mode: this rank's packed frames, film_geo_.slot_words() words each
+    FilmGeo film_geo_;
     u64 census_start_ = 0;
     void sum_series(std::vector<u64>& series, const char* what);  // collective: the ranks' series added up (wrapping)
     // This rank's part of signature(), snapshot() and snapshot_diff().

@@ -135,6 +135,22 @@ int max_signature_depth(Nbhd nbhd = Nbhd::Moore);
 int signature_blocks_per_cu(int k, u32 flags, bool bounded, Nbhd nbhd = Nbhd::Moore);
 void launch_step_signature(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src,
                            u64* dst, const LaneDesc* plan, i64 n_waves, const StepParams& p, u64* slots, hipStream_t s);
+// step_film<K> (film_kernel.hip): step_rule / step_rule_bounded that also stores the words of a board window after
+// every generation of the pass.  `win` is the window in board rows and board words (gol/film.hpp: FilmGeo's r0,
+// rows, w0, fw); the frame of generation g + 1 of the pass's k is the rows x fw words at frames + g * rows * fw
+// (device memory, zeroed by the caller; nullptr: store nothing), of which this launch writes the words its plan's
+// store lanes own, each exactly once.  frames_words: the words the caller owns from `frames` on; a pass that would
+// store past them, or whose k frames reach 2^31 bytes, is refused before the launch.  Plans, StepParams, rows and
+// words of the board read and written, and the argument checks, as launch_step_signature.  Depths 1 .. max_film_depth().
+struct FilmWindow {
+    i64 r0 = 0, rows = 0;  // board row of frame row 0, frame rows
+    i64 w0 = 0, fw = 0;    // board word of frame word 0, words per frame row
+};
+int max_film_depth(Nbhd nbhd = Nbhd::Moore);
+int film_blocks_per_cu(int k, u32 flags, bool bounded, Nbhd nbhd = Nbhd::Moore);
+void launch_step_film(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src, u64* dst,
+                      const LaneDesc* plan, i64 n_waves, const StepParams& p, const FilmWindow& win, u64* frames,
+                      i64 frames_words, hipStream_t s);
 // out[0] += the signature of the tile in `buf` at (grow0, gword0) (wrapping; out zeroed by the caller).
 void launch_signature(const u64* buf, const Layout& L, i64 grow0, i64 gword0, u64* out, hipStream_t s);
 // out[0] += the number of cells of the tile that differ between boards a and b (one layout; out zeroed by the caller).

@@ -111,6 +111,10 @@ py::dict stats_dict(const EngineStats& s) {
     d["boundary"] = s.boundary;
     d["census"] = s.census;
     d["signature"] = s.signature;
+    if (s.film.on)
+        d["film"] = py::make_tuple(s.film.r0, s.film.c0, s.film.rows, s.film.cols);
+    else
+        d["film"] = py::none();
     d["schedule"] = s.schedule;
     d["kernel_depth"] = s.kernel_depth;
     d["tile_waves"] = s.tile_waves;
@@ -286,6 +290,22 @@ PYBIND11_MODULE(_gol, m) {
         .def_readwrite("plan_xcds", &EngineConfig::plan_xcds)
         .def_readwrite("census", &EngineConfig::census)
         .def_readwrite("signature", &EngineConfig::signature)
+        // film mode: None (off) or the window (r0, c0, rows, cols)
+        .def_property(
+            "film",
+            [](const EngineConfig& c) -> py::object {
+                if (!c.film.on) return py::none();
+                return py::make_tuple(c.film.r0, c.film.c0, c.film.rows, c.film.cols);
+            },
+            [](EngineConfig& c, py::object v) {
+                if (v.is_none()) {
+                    c.film = FilmRect();
+                    return;
+                }
+                if (!py::isinstance<py::sequence>(v) || py::len(v) != 4) throw py::value_error("film must be None or (r0, c0, rows, cols)");
+                const py::sequence q = py::reinterpret_borrow<py::sequence>(v);
+                c.film = FilmRect{true, q[0].cast<i64>(), q[1].cast<i64>(), q[2].cast<i64>(), q[3].cast<i64>()};
+            })
         // the life-like rule as a string (any form Rule::parse takes; reads back canonical, B3/S23)
         .def_property(
             "rule", [](const EngineConfig& c) { return c.rule.str(); },
@@ -382,6 +402,25 @@ PYBIND11_MODULE(_gol, m) {
                  return py::make_tuple(s.start, a, b);
              })
         .def("signatures_clear", &Engine::signatures_clear, py::call_guard<py::gil_scoped_release>())
+        // film mode (collective): (start, frames), frames a (n, rows, cols) uint8 array, frame i the window at generation start + 1 + i
+        .def("film",
+             [](Engine& e) {
+                 size_t n = 0;
+                 {
+                     py::gil_scoped_release r;
+                     n = e.film_frames();
+                 }
+                 const FilmRect& w = e.config().film;
+                 py::array_t<u8> a({(py::ssize_t)n, (py::ssize_t)w.rows, (py::ssize_t)w.cols});  // (unpacked in place)
+                 u8* out = a.mutable_data();
+                 u64 start = 0;
+                 {
+                     py::gil_scoped_release r;
+                     start = e.film_into(out, n);
+                 }
+                 return py::make_tuple(start, a);
+             })
+        .def("film_clear", &Engine::film_clear, py::call_guard<py::gil_scoped_release>())
         // any mode (collective): the signature of the current board; a copy of the board, and the cells that differ from it
         .def("signature", &Engine::signature, py::call_guard<py::gil_scoped_release>())
         .def("snapshot", &Engine::snapshot, py::call_guard<py::gil_scoped_release>())
@@ -549,6 +588,8 @@ PYBIND11_MODULE(_gol, m) {
     m.def("hip_set_device", &hip_set_device);
     m.def("max_census_depth", []() { return hipk::max_census_depth(); });  // deepest pass of the census kernel
     m.def("max_signature_depth", []() { return hipk::max_signature_depth(); });  // ... of the signature kernel
+    m.def("max_film_depth", []() { return hipk::max_film_depth(); });            // ... of the film kernel
+    m.attr("film_max_cells") = kFilmMaxCells;                                    // cells of the largest window film mode takes
     m.def(
         "naive_byte_run",
         [](i64 N, int gens, int threads, bool sync_each, u64 seed) {

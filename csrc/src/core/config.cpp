@@ -91,6 +91,9 @@ Options options_from_env() {
     o.census = env_flag("GOL_CENSUS", false) || !o.census_out.empty();
     o.signature_out = env_str("GOL_SIGNATURE_OUT", "");
     o.signature = env_flag("GOL_SIGNATURE", false) || !o.signature_out.empty();
+    o.film = env_str("GOL_FILM", "");
+    o.film_out = env_str("GOL_FILM_OUT", "");
+    if (!o.film_out.empty() && o.film.empty()) throw Error("GOL_FILM_OUT needs GOL_FILM=r0,c0,rows,cols (the window to film)");
     if (o.halo_depth < 0 || o.halo_depth > 128) throw Error("GOL_HALO_DEPTH must be in 1..128 (0 = auto)");
     if (o.kernel_depth < 0 || o.kernel_depth > 64) throw Error("GOL_KERNEL_DEPTH must be in 1..64 (0 = auto)");
     return o;

@@ -172,7 +172,25 @@ void step_rows(const u64* src, u64* dst, const Layout& L, i64 r_lo, i64 r_hi, co
     }
 }
 
-u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges, u64* counts, u64* sigs) {
+namespace {
+
+// The tile's own words of `buf` that are words of the window, into the packed frame (cpu.hpp FilmOut).
+void film_frame(const u64* buf, const Layout& L, const Edges& edges, const FilmGeo& geo, u64* frame) {
+    for (i64 r = 0; r < L.h; ++r) {
+        const i64 fr = geo.frame_row(edges.row0 + r);
+        if (fr >= geo.rows) continue;
+        const u64* row = buf + L.index(r, 0);
+        for (i64 c = 0; c < L.nw; ++c) {
+            const i64 f = geo.frame_word(edges.word0 + c);
+            if (f < geo.fw) frame[fr * geo.fw + f] |= row[c] & storage_mask(c, L.w);
+        }
+    }
+}
+
+}  // namespace
+
+u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges, u64* counts, u64* sigs,
+               const FilmOut& film) {
     if (k < 1 || k > L.R) throw Error(strprintf("superstep depth %d outside 1..%d", k, L.R));
     u64* src = a;
     u64* dst = b;
@@ -182,6 +200,7 @@ u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const E
         step_rows(src, dst, L, -ext, L.h + ext, rule, edges);
         if (counts) counts[g] += population(dst, L);  // the tile's own cells: rows [0, h), words [0, nw), no ghosts
         if (sigs) sigs[g] += signature(dst, L, edges.row0, edges.word0);
+        if (film.frames) film_frame(dst, L, edges, *film.geo, film.frames + (i64)g * film.geo->slot_words());
         std::swap(src, dst);
     }
     return src;

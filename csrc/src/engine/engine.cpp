@@ -60,6 +60,22 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
                 if (cfg_.kernel == k)
                     throw Error("kernel '" + cfg_.kernel + "' records no signatures: the signature kernel runs every pass (use kernel auto or rule)");
     }
+    if (cfg_.film.on) {
+        const FilmRect& f = cfg_.film;
+        if (cfg_.census) throw Error("film together with census: one per-generation record per engine (film mode stores frames, not counts)");
+        if (cfg_.signature) throw Error("film together with signature: one per-generation record per engine (film mode stores frames, not hashes)");
+        if (cfg_.compat) throw Error("film with GOL_COMPAT=reference: compat mode runs the reference's loop, not the film kernel");
+        if (cfg_.subtiles == 2) throw Error("two sub-tiles per rank (GOL_SUBTILES=2) do not run the film kernel");
+        if (cfg_.backend == "hip")
+            for (const char* k : {"temporal", "tile", "pipe", "resident", "lds"})
+                if (cfg_.kernel == k)
+                    throw Error("kernel '" + cfg_.kernel + "' stores no frames: the film kernel runs every pass (use kernel auto or rule)");
+        check_window(f.r0, f.c0, f.rows, f.cols);  // (window()'s checks: names the rectangle and the board)
+        if (f.rows * f.cols > kFilmMaxCells)
+            throw Error(strprintf("film: a window of %lld x %lld cells has more than 2^22 cells; read larger rectangles with window()",
+                                  (long long)f.rows, (long long)f.cols));
+        film_geo_ = FilmGeo(f, g_.dec.H, g_.dec.W);
+    }
     if (t_->size() != g_.dec.P || t_->rank() != g_.rank)
         throw Error(strprintf("transport (rank %d of %d) does not match the geometry (rank %d of %d)", t_->rank(),
                               t_->size(), g_.rank, g_.dec.P));
@@ -103,6 +119,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     stats_.boundary = boundary_name(cfg_.boundary);
     stats_.census = cfg_.census;
     stats_.signature = cfg_.signature;
+    stats_.film = cfg_.film;
     std::string f = env_str("GOL_FAULT", "");
     if (!f.empty()) {
         int fr = -1;
@@ -205,6 +222,7 @@ void Engine::init(const PatternSpec& p) {
     stats_.boundary = boundary_name(cfg_.boundary);
     stats_.census = cfg_.census;
     stats_.signature = cfg_.signature;
+    stats_.film = cfg_.film;
     census_restart(0);
     have_snapshot_ = false;
     if (t_->size() > 1) {
@@ -212,11 +230,17 @@ void Engine::init(const PatternSpec& p) {
         // by reductions every rank sees (so on a mismatch every rank raises and none waits for a peer).  One code:
         // the rule's 32 bits, the boundary above them, the census mode above that (exact in a double).
         // (signature mode one bit above the census mode's)
+        // (film mode one bit above the signature mode's; the window's four numbers are agreed after the modes)
         const double code = (double)cfg_.rule.code() + (double)((u64)cfg_.boundary << 32) + (double)((u64)cfg_.census << 40) +
-                            (double)((u64)cfg_.signature << 41);
+                            (double)((u64)cfg_.signature << 41) + (double)((u64)cfg_.film.on << 42);
         const double lo = t_->allreduce_min(code), hi = t_->allreduce_max(code);
         if (lo != hi) {
-            const u64 clo = (u64)lo, chi = (u64)hi;
+            u64 clo = (u64)lo, chi = (u64)hi;
+            if ((clo >> 42) != (chi >> 42))
+                throw Error(strprintf("the ranks disagree on the film mode: rank %d has film %s (some ranks on, some off)", g_.rank,
+                                      cfg_.film.on ? "on" : "off"));
+            clo &= ((u64)1 << 42) - 1;
+            chi &= ((u64)1 << 42) - 1;
             if ((clo >> 41) != (chi >> 41))
                 throw Error(strprintf("the ranks disagree on the signature mode: rank %d has signature %s (some ranks on, some off)",
                                       g_.rank, cfg_.signature ? "on" : "off"));
@@ -230,6 +254,17 @@ void Engine::init(const PatternSpec& p) {
                                       boundary_name((Boundary)(uhi >> 32))));
             throw Error(strprintf("the ranks disagree on the rule: rank %d has %s (rule codes 0x%x .. 0x%x over the ranks)",
                                   g_.rank, stats_.rule.c_str(), (unsigned)(ulo & 0xFFFFFFFFu), (unsigned)(uhi & 0xFFFFFFFFu)));
+        }
+        if (cfg_.film.on) {  // (on every rank or on none: agreed above)
+            const i64 mine[4] = {cfg_.film.r0, cfg_.film.c0, cfg_.film.rows, cfg_.film.cols};
+            bool same = true;
+            for (i64 v : mine) {
+                const double vlo = t_->allreduce_min((double)v), vhi = t_->allreduce_max((double)v);
+                same = same && vlo == vhi;
+            }
+            if (!same)
+                throw Error(strprintf("the ranks disagree on the film window: rank %d has %lld x %lld cells at (%lld, %lld)", g_.rank,
+                                      (long long)mine[2], (long long)mine[3], (long long)mine[0], (long long)mine[1]));
         }
     }
     do_init(p);
@@ -350,7 +385,51 @@ void Engine::census_restart(u64 generation) {
     census_discard();
     census_host_.clear();
     sig_host_.clear();
+    film_host_.clear();
     census_start_ = generation;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Film (film mode's record: film_host_, this rank's packed frames; gol/film.hpp)
+// ---------------------------------------------------------------------------------------------
+
+Engine::Film Engine::film() {
+    if (!cfg_.film.on)
+        throw Error("film(): this engine is not in film mode (EngineConfig::film, Simulation(film=(r0, c0, rows, cols)), GOL_FILM=r0,c0,rows,cols)");
+    Film out;
+    out.n = film_frames();
+    out.frames.resize(out.n * (size_t)(film_geo_.rows * film_geo_.cols));
+    out.start = film_into(out.frames.data(), out.n);
+    return out;
+}
+
+size_t Engine::film_frames() {
+    if (!cfg_.film.on) throw Error("film(): this engine is not in film mode");
+    census_collect();
+    return film_host_.size() / (size_t)film_geo_.slot_words();
+}
+
+u64 Engine::film_into(u8* out, size_t n) {
+    if (!cfg_.film.on) throw Error("film(): this engine is not in film mode");
+    const size_t slot = (size_t)film_geo_.slot_words();
+    if (n * slot != film_host_.size()) throw Error("film_into(): the record has changed since film_frames()");
+    std::vector<u64> sum;
+    const u64* packed = film_host_.data();
+    if (t_->size() > 1) {  // (every word has one owner: the sum puts the ranks' words side by side)
+        sum = film_host_;
+        sum_series(sum, "film");
+        packed = sum.data();
+    }
+    const i64 rows = film_geo_.rows, cols = film_geo_.cols, fw = film_geo_.fw, total = (i64)n * rows;
+#pragma omp parallel for schedule(static) if (total * cols > 65536)
+    for (i64 r = 0; r < total; ++r) film_geo_.unpack_row(packed + r * fw, out + r * cols);
+    return census_start_;
+}
+
+void Engine::film_clear() {
+    if (!cfg_.film.on) throw Error("film_clear(): this engine is not in film mode");
+    census_collect();
+    census_restart(census_start_ + (u64)(film_host_.size() / (size_t)film_geo_.slot_words()));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -681,7 +760,7 @@ class CpuEngine : public Engine {
             if (self_y()) cpu::fill_ghost_rows_wrap(cur_, L_);
         }
         u64 *counts = nullptr, *sigs = nullptr;
-        if (recording()) {  // this rank's own cells after each of the k generations
+        if (cfg_.census || cfg_.signature) {  // this rank's own cells after each of the k generations
             census_host_.resize(census_host_.size() + (size_t)k, 0);
             counts = census_host_.data() + (census_host_.size() - (size_t)k);
         }
@@ -690,7 +769,13 @@ class CpuEngine : public Engine {
             sigs = sig_host_.data() + (sig_host_.size() - (size_t)k);
         }
         cpu::Edges place(cfg_.boundary, g_);  // (the signature's keys need the tile's place on the torus too)
-        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, place, counts, sigs);
+        cpu::FilmOut film;
+        if (cfg_.film.on) {  // this rank's words of the window after each of the k generations
+            const size_t add = (size_t)k * (size_t)film_geo_.slot_words();
+            film_host_.resize(film_host_.size() + add, 0);
+            film = cpu::FilmOut{&film_geo_, film_host_.data() + (film_host_.size() - add)};
+        }
+        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, place, counts, sigs, film);
         if (res != cur_) std::swap(cur_, oth_);
         if (self_x()) cpu::fill_ghost_cols_wrap(cur_, L_, 0, L_.h);
     }

@@ -18,6 +18,7 @@ const void* nbhd_rule_kernel(Nbhd nbhd, int k, u32 flags);
 const void* nbhd_bounded_kernel(Nbhd nbhd, int k, u32 flags);
 const void* nbhd_census_kernel(Nbhd nbhd, int k, u32 flags, bool bounded);
 const void* nbhd_signature_kernel(Nbhd nbhd, int k, u32 flags, bool bounded);
+const void* nbhd_film_kernel(Nbhd nbhd, int k, u32 flags, bool bounded);  // (step_film: nbhd_film_kernel.hip)
 
 namespace {
 

@@ -1,7 +1,7 @@
-// gol-mi355x: the policies of step_rule_bounded, step_census and step_signature (rule_runner.hpp tells what a policy
-// is), in a header because each has two kernels: the Moore one in rule_bounded_kernel.hip, census_kernel.hip and
-// signature_kernel.hip, whose headers explain the policies, and the von Neumann / hexagonal one in the nbhd_*.hip
-// unit of the same family.
+// gol-mi355x: the policies of step_rule_bounded, step_census, step_signature and step_film (rule_runner.hpp tells what
+// a policy is), in a header because each has two kernels: the Moore one in rule_bounded_kernel.hip, census_kernel.hip,
+// signature_kernel.hip and film_kernel.hip, whose headers explain the policies, and the von Neumann / hexagonal one in
+// the nbhd_*.hip unit of the same family.
 #pragma once
 
 #include "gol/signature.hpp"
@@ -146,6 +146,60 @@ struct SigPolicy {
                           ((unsigned long long)s_hi << 32) | (unsigned long long)s_lo);
             }
         }
+    }
+};
+
+// step_film's kernel argument: where the frames of the pass go and which cells are the window's (gol/film.hpp).
+struct FilmArgs {
+    uint2* frames;   // the slot of the pass's first generation (device memory; nullptr: store nothing)
+    u32 slot_words;  // u64 words from one generation's frame to the next: rows * fw
+    u32 rows, fw;    // the frame: window rows x board words
+    i32 r0, w0;      // board row and board word of frame row 0, frame word 0 (inside the board)
+};
+
+// step_film: the owned words of every level's output that lie in the window go to the level's frame.
+template <int K, int MASK, bool BOUNDED>
+struct FilmPolicy {
+    static constexpr int kRowBarriers = 2;
+    EdgeMask<MASK> em;  // BOUNDED
+    OwnMask<MASK> own;
+    uint2* const frames;  // (uniform)
+    const u32 slot_words, rows, fw;
+    u32 widx;  // the lane's word in a frame row; kNoWord: the lane owns no word of the window
+    int d0;    // board row of row counter t = 0, less the window's first row: grow0 + row0 - K - r0
+    int H;     // rows of the board
+    static constexpr u32 kNoWord = ~0u;
+    struct Tally {};
+
+    __device__ __forceinline__ FilmPolicy(const LaneDesc& d, int nrows, const StepParams& p, const TileArgs& ta,
+                                          const FilmArgs& fa)
+        : frames(fa.frames), slot_words(fa.slot_words), rows(fa.rows), fw(fa.fw) {
+        const bool stores = d.flags & LANE_STORE;  // (ahead of the masks: the prologue's order, PERFORMANCE.md section 23)
+        if (BOUNDED) em.template init<K>(d, ta);
+        own.template init<K>(stores, d, nrows, p, ta);
+        // the lane's word: an owned word of the tile is a word of the board, (gword - w0) mod gwords its place in a frame row
+        int f = (int)(ta.gword0 + d.col) - fa.w0;
+        f += f < 0 ? (int)ta.gwords : 0;
+        const bool owns = (own.own_lo | own.own_hi) != 0;
+        widx = owns && (u32)f < fa.fw ? (u32)f : kNoWord;
+        const int db = (int)(ta.grow0 + (i64)d.row0 - K) - fa.r0;
+        d0 = MASK == MASK_UNI ? __builtin_amdgcn_readfirstlane(db) : db;
+        H = (int)ta.grows;
+    }
+
+    // (BOUNDED) the loaded row: ghost rows and words hold the torus neighbour's cells
+    __device__ __forceinline__ void input(u32& lo, u32& hi, int i) const {
+        if (BOUNDED) em.apply(lo, hi, i);
+    }
+    // The (masked) output of level l: an owned row is a row of the tile, so of the board, and its distance from the
+    // window's first row is d0 + t or, before that row, H more: the row test and the frame row at once.
+    __device__ __forceinline__ void level(Tally&, int l, u32& lo, u32& hi, int t) const {
+        if (BOUNDED) em.apply(lo, hi, t);
+        if (!frames) return;  // (uniform)
+        int dist = d0 + t;
+        dist += dist < 0 ? H : 0;
+        if ((u32)(t - own.Ao) < own.ospan && (u32)dist < rows && widx != kNoWord)
+            frames[(u32)l * slot_words + (u32)dist * fw + widx] = make_uint2(lo & own.own_lo, hi & own.own_hi);
     }
 };
 

@@ -170,6 +170,7 @@ EngineConfig engine_config(const Options& o, const std::string& backend, int dev
     c.boundary = parse_boundary(o.boundary.empty() ? env_str("GOL_BOUNDARY", "torus") : o.boundary);
     c.census = o.census;
     c.signature = o.signature;
+    if (!o.film.empty()) c.film = parse_film(o.film);
     c.tile_waves = (int)env_int("GOL_TILE_WAVES", 8);
     c.tune_tile_waves = getenv("GOL_TILE_WAVES") == nullptr;
     c.transport = (o.transport == "rccl" || o.transport == "p2p") ? "device" : o.transport;
@@ -451,6 +452,10 @@ void write_metrics(const Options& o, Engine& eng, const CliArgs& a, double durat
     f << "  \"boundary\": \"" << s.boundary << "\",\n";
     f << "  \"census\": " << (s.census ? "true" : "false") << ",\n";
     f << "  \"signature\": " << (s.signature ? "true" : "false") << ",\n";
+    if (s.film.on)
+        f << "  \"film\": [" << s.film.r0 << ", " << s.film.c0 << ", " << s.film.rows << ", " << s.film.cols << "],\n";
+    else
+        f << "  \"film\": null,\n";
     f << "  \"schedule\": \"" << s.schedule << "\",\n";
     f << "  \"autotune\": \"" << s.tuning << "\",\n";
     f << "  \"plan_waves\": " << s.plan_waves << ",\n  \"lane_efficiency\": " << s.lane_efficiency << ",\n";
@@ -532,6 +537,15 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
             throw Error(strprintf("GOL_RLE_OUT: the %lld x %lld board has more than 2^26 cells, too large to gather on rank 0 "
                                   "and write as RLE (a checkpoint, GOL_CHECKPOINT_EVERY, holds any board)",
                                   (long long)dec.H, (long long)dec.W));
+        constexpr u64 kFilmOutMaxBytes = (u64)1 << 30;
+        if (!o.film_out.empty()) {
+            const FilmRect fr = parse_film(o.film);
+            if (fr.rows >= 1 && fr.cols >= 1 && fr.rows * fr.cols <= kFilmMaxCells &&  // (else: the engine refuses the window)
+                (u64)a.iterations * (u64)(fr.rows * fr.cols) > kFilmOutMaxBytes)
+                throw Error(strprintf("GOL_FILM_OUT: %llu iterations x %lld rows x %lld columns are more than 2^30 bytes of frames; "
+                                      "film a smaller window or run fewer iterations",
+                                      (unsigned long long)a.iterations, (long long)fr.rows, (long long)fr.cols));
+        }
         PatternSpec pat = make_pattern(a.pattern, dec, o.seed);
         std::shared_ptr<Transport> t = make_data_transport(control, backend, o, device);
         EngineConfig ec = engine_config(o, backend, device);
@@ -616,6 +630,28 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
             t->broadcast(&ok, sizeof(ok), 0);
             if (!ok) throw Error("GOL_SIGNATURE_OUT: cannot write " + o.signature_out);
         }
+        if (!o.film_out.empty()) {
+            // the run's frames (collective); rank 0 writes them as .npy version 1.0, and every rank learns whether that worked
+            const Engine::Film fm = eng->film();
+            u64 ok = 1;
+            if (rank == 0) {
+                std::string hdr = strprintf("{'descr': '|u1', 'fortran_order': False, 'shape': (%zu, %lld, %lld), }", fm.n,
+                                            (long long)ec.film.rows, (long long)ec.film.cols);
+                hdr.append(63 - (10 + hdr.size()) % 64, ' ');  // magic, version and length take 10 bytes: data at a multiple of 64
+                hdr.push_back('\n');
+                const unsigned char pre[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(hdr.size() & 0xFF),
+                                               (unsigned char)(hdr.size() >> 8)};
+                FILE* cf = fopen(o.film_out.c_str(), "wb");
+                ok = cf != nullptr;
+                if (cf) {
+                    ok = fwrite(pre, 1, sizeof(pre), cf) == sizeof(pre) && fwrite(hdr.data(), 1, hdr.size(), cf) == hdr.size() &&
+                         (fm.frames.empty() || fwrite(fm.frames.data(), 1, fm.frames.size(), cf) == fm.frames.size());
+                    ok = (fclose(cf) == 0) && ok;
+                }
+            }
+            t->broadcast(&ok, sizeof(ok), 0);
+            if (!ok) throw Error("GOL_FILM_OUT: cannot write " + o.film_out);
+        }
         if (!o.rle_out.empty()) {
             RlePattern out;
             out.rows = dec.H;
@@ -661,6 +697,7 @@ int run_cli(int argc, char** argv) {
         // with the parse error, before any rank starts
         (void)Rule::parse(env_str("GOL_RULE", "B3/S23"));  // (GOL_VERBOSE=1: describe() names the rule)
         (void)parse_boundary(env_str("GOL_BOUNDARY", "torus"));  // GOL_BOUNDARY likewise
+        if (!o.film.empty()) (void)parse_film(o.film);           // GOL_FILM likewise
         // GOL_PATTERN_FILE likewise: an unreadable file, or one whose rule GOL_RULE contradicts, ends the job here
         const CliPattern cp = load_cli_pattern(o);
         LaunchInfo li = detect_launch(o);

@@ -78,6 +78,13 @@ class Simulation:
                   boundary (generic-kernel speed, B3/S23 included; passes of at most ``max_signature_depth``
                   generations, eager launches); without ``census`` (it records the population already),
                   ``compat``, ``subtiles=2`` or the specialised kernels.
+    film:         film mode (default off; GOL_FILM=r0,c0,rows,cols): ``(r0, c0, rows, cols)``, a window of the global board
+                  in :meth:`window`'s coordinates (they wrap on the torus; on a bounded board the window lies inside; at most
+                  2^22 cells).  Every generation :meth:`step` computes also yields the window's cells in that generation,
+                  read with :meth:`film`.  HIP: the film kernel ``step_film`` stores the window's words inside every pass,
+                  for every rule, neighbourhood and either boundary (generic-kernel speed, B3/S23 included; passes of at
+                  most ``max_film_depth`` generations, eager launches; the frames wait in a device buffer of GOL_FILM_MB
+                  MiB, default 64); without ``census``, ``signature``, ``compat``, ``subtiles=2`` or the specialised kernels.
     compat:       reproduce the reference's halo quirks (frozen gen-0 halos, P<=2 swap).
     watchdog:     seconds without progress before the job is aborted (0 = off; GOL_WATCHDOG).
     """
@@ -115,6 +122,7 @@ class Simulation:
         boundary: Optional[str] = None,
         census: Optional[bool] = None,
         signature: Optional[bool] = None,
+        film=None,
     ):
         self.transport = transport if transport is not None else _gol.SelfTransport()
         P, rank = self.transport.size(), self.transport.rank()
@@ -179,6 +187,45 @@ class Simulation:
                     f"signature=True: kernel_depth {kernel_depth} exceeds the signature kernel's deepest pass, "
                     f"{_gol.max_signature_depth()} generations"
                 )
+        if film is None:  # (read per call, as the census mode is)
+            env = os.environ.get("GOL_FILM", "")
+            if env:
+                try:
+                    film = tuple(int(v) for v in env.split(","))
+                except ValueError:
+                    film = ()
+                if len(film) != 4:
+                    raise ValueError(f"GOL_FILM must be r0,c0,rows,cols (got {env!r})")
+        if film is not None:
+            film = tuple(int(v) for v in film)
+            if len(film) != 4:
+                raise ValueError(f"film must be (r0, c0, rows, cols), got {film!r}")
+            r0, c0, rows, cols = film
+            H, W = self.decomposition.H, self.decomposition.W
+            if cfg.census or cfg.signature:
+                raise ValueError("film with census=True or signature=True: one per-generation record per simulation")
+            if compat:
+                raise ValueError("film with compat=True: compat mode runs the reference's loop, not the film kernel")
+            if int(subtiles) == 2:
+                raise ValueError("film with subtiles=2: the sub-tile halves do not run the film kernel")
+            if self.backend == "hip" and kernel in ("temporal", "tile", "pipe", "resident", "lds"):
+                raise ValueError(f"kernel {kernel!r} stores no frames: the film kernel runs every pass (use auto or rule)")
+            if self.backend == "hip" and int(kernel_depth) > _gol.max_film_depth():
+                raise ValueError(
+                    f"film: kernel_depth {kernel_depth} exceeds the film kernel's deepest pass, "
+                    f"{_gol.max_film_depth()} generations"
+                )
+            if not (1 <= rows <= H and 1 <= cols <= W):
+                raise ValueError(f"film: a window of {rows} x {cols} cells: rows must be in 1..{H} and columns in 1..{W} (the board)")
+            if cfg.boundary == "dead" and (r0 < 0 or c0 < 0 or r0 + rows > H or c0 + cols > W):
+                raise ValueError(
+                    f"film: the {rows} x {cols} rectangle at ({r0}, {c0}) does not lie inside the bounded {H} x {W} board"
+                )
+            if rows * cols > _gol.film_max_cells:
+                raise ValueError(
+                    f"film: a window of {rows} x {cols} cells has more than 2^22 cells; read larger rectangles with window()"
+                )
+            cfg.film = film
         cfg.subtiles = int(subtiles)  # 2 / 0 / -1 auto: two sub-tiles per rank on two streams (HIP, 1-D)
         cfg.run_hint = int(run_hint)  # generations of the runs to come: one replay graph covers them
         cfg.rows_per_wave = rows_per_wave
@@ -287,6 +334,23 @@ class Simulation:
         if not self.config.signature:
             raise ValueError("signatures_clear() needs a simulation built with signature=True (or GOL_SIGNATURE=1)")
         self.engine.signatures_clear()
+
+    def film(self):
+        """``(start, frames)``: ``frames[i]`` is what ``window(r0, c0, rows, cols)`` would return at generation
+        ``start + 1 + i``, a ``(n, rows, cols)`` uint8 array with one frame per generation computed since the record was
+        cleared (by :meth:`init`, :meth:`load_rle`, :meth:`restore` or :meth:`film_clear`; :meth:`stamp` and
+        :meth:`set_board` leave it running).  Collective; every rank gets the same array (:func:`ops.numpy_film` is its
+        oracle).  Needs ``film=(r0, c0, rows, cols)``."""
+        if self.config.film is None:
+            raise ValueError("film() needs a simulation built with film=(r0, c0, rows, cols) (or GOL_FILM)")
+        start, frames = self.engine.film()
+        return int(start), frames
+
+    def film_clear(self) -> None:
+        """Forget the recorded frames; the next record starts at the generation reached."""
+        if self.config.film is None:
+            raise ValueError("film_clear() needs a simulation built with film=(r0, c0, rows, cols) (or GOL_FILM)")
+        self.engine.film_clear()
 
     def snapshot(self) -> None:
         """Keep a copy of the current board (a third board buffer, allocated on first use) for :meth:`snapshot_diff`."""

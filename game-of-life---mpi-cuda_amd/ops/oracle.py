@@ -222,6 +222,23 @@ def numpy_signatures(board: np.ndarray, rule, gens: int, bounded: bool = False, 
     return (sigs, b) if return_board else sigs
 
 
+def numpy_film(board: np.ndarray, rule, gens: int, rect, bounded: bool = False, return_board: bool = False):
+    """The window ``rect = (r0, c0, rows, cols)`` of ``board`` after generations ``1 .. gens`` under ``rule`` as a
+    ``(gens, rows, cols)`` uint8 array (the oracle of the engines' film mode), on the torus or, ``bounded``, on a board
+    with dead edges.  One generation of :func:`numpy_step_rule` / :func:`numpy_step_rule_bounded` at a time; each frame
+    is taken with ``np.take(..., mode="wrap")`` on both axes, so the window's coordinates wrap as ``window()``'s do.
+    ``return_board`` also returns the last board."""
+    step = numpy_step_rule_bounded if bounded else numpy_step_rule
+    r0, c0, rows, cols = (int(v) for v in rect)
+    b = np.asarray(board, dtype=np.uint8)
+    frames = np.zeros((int(gens), rows, cols), dtype=np.uint8)
+    ri, ci = np.arange(r0, r0 + rows), np.arange(c0, c0 + cols)
+    for g in range(int(gens)):
+        b = step(b, rule, 1)
+        frames[g] = np.take(np.take(b, ri, axis=0, mode="wrap"), ci, axis=1, mode="wrap")
+    return (frames, b) if return_board else frames
+
+
 def torch_step_rule(board, rule, generations: int = 1, device=None):
     """A life-like rule on a torus with torch conv2d (fp32, exact for counts <= 8).  Returns a torch uint8 tensor."""
     import torch
