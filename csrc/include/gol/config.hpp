@@ -60,6 +60,10 @@ struct Options {
     std::string film = "";          // GOL_FILM=r0,c0,rows,cols  film mode: that window of the board in every generation of the run
     std::string film_out = "";      // GOL_FILM_OUT  needs GOL_FILM; rank 0 writes the frames there as a NumPy .npy file (uint8,
                                     // shape (iterations, rows, cols))
+    std::string density_film = "";      // GOL_DENSITY_FILM=block_rows[,block_cols]  density-film mode: the density map of the
+                                        // whole board in every generation of the run
+    std::string density_film_out = "";  // GOL_DENSITY_FILM_OUT  needs GOL_DENSITY_FILM; rank 0 writes the maps there as a NumPy
+                                        // .npy file (uint32, shape (iterations, grid_rows, grid_cols))
     std::string rle_out = "";       // GOL_RLE_OUT  rank 0 writes the final global board as RLE (<= 2^26 cells)
     std::string rule = "";          // the run's rule when GOL_PATTERN_FILE names one and GOL_RULE is unset
     std::string boundary = "";      // the run's boundary when GOL_PATTERN_FILE names a topology and GOL_BOUNDARY is

@@ -7,6 +7,7 @@
 // generation) so no exchange is needed inside the superstep.
 #pragma once
 
+#include "gol/density_film.hpp"
 #include "gol/film.hpp"
 #include "gol/geometry.hpp"
 #include "gol/pattern.hpp"
@@ -56,8 +57,16 @@ struct FilmOut {
     const FilmGeo* geo = nullptr;
     u64* frames = nullptr;  // k frames
 };
+// density (density-film mode; maps == nullptr: none): maps + g * geo->slot_words() is the slot (gol/density_film.hpp)
+// after generation g + 1: the live cells of the tile's own words (the same cells) are added to the counts of their
+// blocks of the global board, found from edges.row0 and edges.word0.
+struct DensityOut {
+    const DensityGeo* geo = nullptr;
+    u64* maps = nullptr;  // k slots
+};
 u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule = Rule(), const Edges& edges = Edges(),
-               u64* counts = nullptr, u64* sigs = nullptr, const FilmOut& film = FilmOut());
+               u64* counts = nullptr, u64* sigs = nullptr, const FilmOut& film = FilmOut(),
+               const DensityOut& density = DensityOut());
 
 // x-periodic ghost words (and tail ghost bits) for rows [r_lo, r_hi).
 void fill_ghost_cols_wrap(u64* buf, const Layout& L, i64 r_lo, i64 r_hi);

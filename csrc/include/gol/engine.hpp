@@ -23,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "gol/density_film.hpp"
 #include "gol/film.hpp"
 #include "gol/geometry.hpp"
 #include "gol/pattern.hpp"
@@ -70,6 +71,10 @@ struct EngineConfig {
                                       // the cells of that window of the global board, window()'s coordinates and checks
                                       // (Engine::film).  HIP: step_film stores them inside every pass.  Not together with
                                       // census or signature
+    DensityBlocks density_film;       // density-film mode (GOL_DENSITY_FILM=block_rows[,block_cols]): every generation run()
+                                      // computes also yields the density(block_rows, block_cols) grid of the global
+                                      // board (Engine::density_film).  HIP: step_density counts it inside every pass.
+                                      // Not together with census, signature or film
     int tile_waves = 8;               // tile kernel: waves per workgroup (4, 8, 16)
     bool tune_tile_waves = true;      // GOL_KERNEL=auto may also try 8 waves (false: GOL_TILE_WAVES set)
     std::string transport = "auto";   // auto | device | host  (host = stage halos through host memory)
@@ -121,6 +126,7 @@ struct EngineStats {
     bool census = false;       // census mode
     bool signature = false;    // signature mode
     FilmRect film;             // film mode: the window (on = false: off)
+    DensityBlocks density_film;  // density-film mode: the blocks (on = false: off)
     std::string schedule;      // superstep schedule: local (no neighbours) | split | full
     std::string tuning;        // init-time measurements behind the auto choices (HIP)
     bool registered = false;   // HIP + RCCL: the boards are registered with the communicator (zero-copy halos)
@@ -181,7 +187,9 @@ class Engine {
     // differ between the current board and the snapshot; throws, before any communication, without a snapshot.
     void snapshot();
     u64 snapshot_diff();
-    bool recording() const { return cfg_.census || cfg_.signature || cfg_.film.on; }  // run() keeps a per-generation record
+    bool recording() const {  // run() keeps a per-generation record
+        return cfg_.census || cfg_.signature || cfg_.film.on || cfg_.density_film.on;
+    }
 
     // ----- film (EngineConfig::film) -----
     // Collective: (start, n, frames): frame i, rows x cols 0/1 bytes at frames[i * rows * cols], is what
@@ -203,6 +211,28 @@ class Engine {
     size_t film_frames();
     u64 film_into(u8* out, size_t n);
     const FilmGeo& film_geo() const { return film_geo_; }
+
+    // ----- density film (EngineConfig::density_film) -----
+    // Collective: (start, n, maps): map i, grid_rows x grid_cols counts at maps[i * grid_rows * grid_cols], is what
+    // density(block_rows, block_cols) would return at generation start + 1 + i, for every generation run() has
+    // computed since the record was cleared; the start, clear and restart rules are the census's (census_restart
+    // serves this mode too).  The same on every rank: each rank counts the cells it owns (gol/density_film.hpp) and
+    // the ranks' maps are summed over the control plane, a few maps at a time.  Throws, before any communication, on
+    // an engine that is not in density-film mode.
+    struct DensityFilm {
+        u64 start = 0;
+        size_t n = 0;
+        std::vector<u32> maps;
+    };
+    DensityFilm density_film();
+    void density_film_clear();
+    // density_film() in two steps, for a caller that owns the counts: density_film_frames() brings this rank's record
+    // to the host and returns its maps (the same number on every rank; no communication); density_film_into() is the
+    // collective part and writes the summed maps into out (n * grid_rows * grid_cols counts, n as returned); it
+    // returns start.
+    size_t density_film_frames();
+    u64 density_film_into(u32* out, size_t n);
+    const DensityGeo& density_geo() const { return density_geo_; }
 
     // ----- views and pattern stamping -----
     // Global board coordinates on the torus: a window or a pattern may start anywhere (r0, c0 are taken
@@ -343,6 +373,8 @@ class Engine {
     std::vector<u64> census_host_, sig_host_;
     std::vector<u64> film_host_;  // film mode: this rank's packed frames, film_geo_.slot_words() words each
     FilmGeo film_geo_;
+    std::vector<u64> density_host_;  // density-film mode: this rank's maps, density_geo_.slot_words() words each
+    DensityGeo density_geo_;
     u64 census_start_ = 0;
     void sum_series(std::vector<u64>& series, const char* what);  // collective: the ranks' series added up (wrapping)
     // This rank's part of signature(), snapshot() and snapshot_diff().

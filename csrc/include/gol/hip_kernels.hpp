@@ -36,6 +36,7 @@
 
 #include <vector>
 
+#include "gol/density_film.hpp"
 #include "gol/geometry.hpp"
 #include "gol/plan.hpp"
 #include "gol/rule.hpp"
@@ -151,6 +152,19 @@ int film_blocks_per_cu(int k, u32 flags, bool bounded, Nbhd nbhd = Nbhd::Moore);
 void launch_step_film(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src, u64* dst,
                       const LaneDesc* plan, i64 n_waves, const StepParams& p, const FilmWindow& win, u64* frames,
                       i64 frames_words, hipStream_t s);
+// step_density<K> (density_kernel.hip): step_rule / step_rule_bounded that also counts the live cells of every block
+// of the global board after every generation of the pass.  `grid` is the block shape and the grid
+// (gol/density_film.hpp: DensityGeo, with blocks no larger than the board); the map of generation g + 1 of the pass's k is the grid_rows x grid_cols u32 at
+// maps + g * slot words, slot = ceil(grid_rows * grid_cols / 2) (device memory, zeroed by the caller; nullptr: count
+// nothing), to which this launch adds the cells its plan's store lanes own, each exactly once.  maps_words: the
+// words the caller owns from `maps` on; a pass whose k maps do not fit them is refused before the launch.  Plans,
+// StepParams, rows and words of the board read and written, and the argument checks, as launch_step_signature.
+// Depths 1 .. max_density_depth().
+int max_density_depth(Nbhd nbhd = Nbhd::Moore);
+int density_blocks_per_cu(int k, u32 flags, bool bounded, Nbhd nbhd = Nbhd::Moore);
+void launch_step_density(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src, u64* dst,
+                         const LaneDesc* plan, i64 n_waves, const StepParams& p, const DensityGeo& grid, u64* maps,
+                         i64 maps_words, hipStream_t s);
 // out[0] += the signature of the tile in `buf` at (grow0, gword0) (wrapping; out zeroed by the caller).
 void launch_signature(const u64* buf, const Layout& L, i64 grow0, i64 gword0, u64* out, hipStream_t s);
 // out[0] += the number of cells of the tile that differ between boards a and b (one layout; out zeroed by the caller).

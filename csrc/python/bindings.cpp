@@ -115,6 +115,10 @@ py::dict stats_dict(const EngineStats& s) {
         d["film"] = py::make_tuple(s.film.r0, s.film.c0, s.film.rows, s.film.cols);
     else
         d["film"] = py::none();
+    if (s.density_film.on)
+        d["density_film"] = py::make_tuple(s.density_film.rows, s.density_film.cols);
+    else
+        d["density_film"] = py::none();
     d["schedule"] = s.schedule;
     d["kernel_depth"] = s.kernel_depth;
     d["tile_waves"] = s.tile_waves;
@@ -306,6 +310,23 @@ PYBIND11_MODULE(_gol, m) {
                 const py::sequence q = py::reinterpret_borrow<py::sequence>(v);
                 c.film = FilmRect{true, q[0].cast<i64>(), q[1].cast<i64>(), q[2].cast<i64>(), q[3].cast<i64>()};
             })
+        // density-film mode: None (off) or the blocks (block_rows, block_cols)
+        .def_property(
+            "density_film",
+            [](const EngineConfig& c) -> py::object {
+                if (!c.density_film.on) return py::none();
+                return py::make_tuple(c.density_film.rows, c.density_film.cols);
+            },
+            [](EngineConfig& c, py::object v) {
+                if (v.is_none()) {
+                    c.density_film = DensityBlocks();
+                    return;
+                }
+                if (!py::isinstance<py::sequence>(v) || py::len(v) != 2)
+                    throw py::value_error("density_film must be None or (block_rows, block_cols)");
+                const py::sequence q = py::reinterpret_borrow<py::sequence>(v);
+                c.density_film = DensityBlocks{true, q[0].cast<i64>(), q[1].cast<i64>()};
+            })
         // the life-like rule as a string (any form Rule::parse takes; reads back canonical, B3/S23)
         .def_property(
             "rule", [](const EngineConfig& c) { return c.rule.str(); },
@@ -421,6 +442,26 @@ PYBIND11_MODULE(_gol, m) {
                  return py::make_tuple(start, a);
              })
         .def("film_clear", &Engine::film_clear, py::call_guard<py::gil_scoped_release>())
+        // density-film mode (collective): (start, maps), maps a (n, grid_rows, grid_cols) uint32 array, map i the density grid
+        // at generation start + 1 + i
+        .def("density_film",
+             [](Engine& e) {
+                 size_t n = 0;
+                 {
+                     py::gil_scoped_release r;
+                     n = e.density_film_frames();
+                 }
+                 const DensityGeo& g = e.density_geo();
+                 py::array_t<u32> a({(py::ssize_t)n, (py::ssize_t)g.grid_rows, (py::ssize_t)g.grid_cols});  // (summed in place)
+                 u32* out = a.mutable_data();
+                 u64 start = 0;
+                 {
+                     py::gil_scoped_release r;
+                     start = e.density_film_into(out, n);
+                 }
+                 return py::make_tuple(start, a);
+             })
+        .def("density_film_clear", &Engine::density_film_clear, py::call_guard<py::gil_scoped_release>())
         // any mode (collective): the signature of the current board; a copy of the board, and the cells that differ from it
         .def("signature", &Engine::signature, py::call_guard<py::gil_scoped_release>())
         .def("snapshot", &Engine::snapshot, py::call_guard<py::gil_scoped_release>())
@@ -589,6 +630,8 @@ PYBIND11_MODULE(_gol, m) {
     m.def("max_census_depth", []() { return hipk::max_census_depth(); });  // deepest pass of the census kernel
     m.def("max_signature_depth", []() { return hipk::max_signature_depth(); });  // ... of the signature kernel
     m.def("max_film_depth", []() { return hipk::max_film_depth(); });            // ... of the film kernel
+    m.def("max_density_depth", []() { return hipk::max_density_depth(); });      // ... of the density kernel
+    m.attr("density_film_max_blocks") = kDensityFilmMaxBlocks;                   // blocks of the finest grid density-film mode takes
     m.attr("film_max_cells") = kFilmMaxCells;                                    // cells of the largest window film mode takes
     m.def(
         "naive_byte_run",

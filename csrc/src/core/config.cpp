@@ -94,6 +94,10 @@ Options options_from_env() {
     o.film = env_str("GOL_FILM", "");
     o.film_out = env_str("GOL_FILM_OUT", "");
     if (!o.film_out.empty() && o.film.empty()) throw Error("GOL_FILM_OUT needs GOL_FILM=r0,c0,rows,cols (the window to film)");
+    o.density_film = env_str("GOL_DENSITY_FILM", "");
+    o.density_film_out = env_str("GOL_DENSITY_FILM_OUT", "");
+    if (!o.density_film_out.empty() && o.density_film.empty())
+        throw Error("GOL_DENSITY_FILM_OUT needs GOL_DENSITY_FILM=block_rows[,block_cols] (the blocks of the maps)");
     if (o.halo_depth < 0 || o.halo_depth > 128) throw Error("GOL_HALO_DEPTH must be in 1..128 (0 = auto)");
     if (o.kernel_depth < 0 || o.kernel_depth > 64) throw Error("GOL_KERNEL_DEPTH must be in 1..64 (0 = auto)");
     return o;

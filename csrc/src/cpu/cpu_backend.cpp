@@ -187,10 +187,24 @@ void film_frame(const u64* buf, const Layout& L, const Edges& edges, const FilmG
     }
 }
 
+// The live cells of the tile's own words of `buf`, added to the counts of their blocks (cpu.hpp DensityOut).
+void density_map(const u64* buf, const Layout& L, const Edges& edges, const DensityGeo& geo, u64* slot) {
+    // (the slot is u64 words, two counts each: counted in u32 of their own and copied over, not through a cast pointer)
+    std::vector<u32> counts((size_t)(2 * geo.slot_words()));
+    memcpy(counts.data(), slot, counts.size() * sizeof(u32));
+    for (i64 r = 0; r < L.h; ++r) {
+        const u64* row = buf + L.index(r, 0);
+        u32* line = counts.data() + ((edges.row0 + r) / geo.block_rows) * geo.grid_cols;
+        for (i64 c = 0; c < L.nw; ++c)
+            line[(edges.word0 + c) / geo.block_words] += (u32)__builtin_popcountll(row[c] & storage_mask(c, L.w));
+    }
+    memcpy(slot, counts.data(), counts.size() * sizeof(u32));
+}
+
 }  // namespace
 
 u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges, u64* counts, u64* sigs,
-               const FilmOut& film) {
+               const FilmOut& film, const DensityOut& density) {
     if (k < 1 || k > L.R) throw Error(strprintf("superstep depth %d outside 1..%d", k, L.R));
     u64* src = a;
     u64* dst = b;
@@ -201,6 +215,7 @@ u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const E
         if (counts) counts[g] += population(dst, L);  // the tile's own cells: rows [0, h), words [0, nw), no ghosts
         if (sigs) sigs[g] += signature(dst, L, edges.row0, edges.word0);
         if (film.frames) film_frame(dst, L, edges, *film.geo, film.frames + (i64)g * film.geo->slot_words());
+        if (density.maps) density_map(dst, L, edges, *density.geo, density.maps + (i64)g * density.geo->slot_words());
         std::swap(src, dst);
     }
     return src;

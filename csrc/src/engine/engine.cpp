@@ -76,6 +76,31 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
                                   (long long)f.rows, (long long)f.cols));
         film_geo_ = FilmGeo(f, g_.dec.H, g_.dec.W);
     }
+    if (cfg_.density_film.on) {
+        const DensityBlocks& b = cfg_.density_film;
+        if (cfg_.census) throw Error("density_film together with census: one per-generation record per engine (density-film mode stores maps, not one count)");
+        if (cfg_.signature) throw Error("density_film together with signature: one per-generation record per engine (density-film mode stores maps, not hashes)");
+        if (cfg_.film.on) throw Error("density_film together with film: one per-generation record per engine (density-film mode stores maps, not frames)");
+        if (cfg_.compat) throw Error("density_film with GOL_COMPAT=reference: compat mode runs the reference's loop, not the density kernel");
+        if (cfg_.subtiles == 2) throw Error("two sub-tiles per rank (GOL_SUBTILES=2) do not run the density kernel");
+        if (cfg_.backend == "hip")
+            for (const char* k : {"temporal", "tile", "pipe", "resident", "lds"})
+                if (cfg_.kernel == k)
+                    throw Error("kernel '" + cfg_.kernel + "' counts no density maps: the density kernel runs every pass (use kernel auto or rule)");
+        // density()'s checks; the one of a block's size first, in words that name the shape
+        if (b.rows >= 1 && b.cols >= 64 && b.cols % 64 == 0 &&
+            std::min(b.rows, g_.dec.H) > (i64)0xFFFFFFFFll / std::min(b.cols, round_up(g_.dec.W, 64)))
+            throw Error(strprintf("density_film: a block of %lld x %lld cells on the %lld x %lld board holds more than 2^32 - 1 cells, "
+                                  "its count would not fit",
+                                  (long long)b.rows, (long long)b.cols, (long long)g_.dec.H, (long long)g_.dec.W));
+        check_density(b.rows, b.cols);
+        if (ceil_div(g_.dec.H, b.rows) > kDensityFilmMaxBlocks / ceil_div(g_.dec.W, b.cols))
+            throw Error(strprintf("density_film: blocks of %lld x %lld cells make a grid of %lld x %lld blocks, more than 2^20 per "
+                                  "generation; read finer grids with density()",
+                                  (long long)b.rows, (long long)b.cols, (long long)ceil_div(g_.dec.H, b.rows),
+                                  (long long)ceil_div(g_.dec.W, b.cols)));
+        density_geo_ = DensityGeo(b, g_.dec.H, g_.dec.W);
+    }
     if (t_->size() != g_.dec.P || t_->rank() != g_.rank)
         throw Error(strprintf("transport (rank %d of %d) does not match the geometry (rank %d of %d)", t_->rank(),
                               t_->size(), g_.rank, g_.dec.P));
@@ -120,6 +145,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     stats_.census = cfg_.census;
     stats_.signature = cfg_.signature;
     stats_.film = cfg_.film;
+    stats_.density_film = cfg_.density_film;
     std::string f = env_str("GOL_FAULT", "");
     if (!f.empty()) {
         int fr = -1;
@@ -223,6 +249,7 @@ void Engine::init(const PatternSpec& p) {
     stats_.census = cfg_.census;
     stats_.signature = cfg_.signature;
     stats_.film = cfg_.film;
+    stats_.density_film = cfg_.density_film;
     census_restart(0);
     have_snapshot_ = false;
     if (t_->size() > 1) {
@@ -232,10 +259,16 @@ void Engine::init(const PatternSpec& p) {
         // (signature mode one bit above the census mode's)
         // (film mode one bit above the signature mode's; the window's four numbers are agreed after the modes)
         const double code = (double)cfg_.rule.code() + (double)((u64)cfg_.boundary << 32) + (double)((u64)cfg_.census << 40) +
-                            (double)((u64)cfg_.signature << 41) + (double)((u64)cfg_.film.on << 42);
+                            (double)((u64)cfg_.signature << 41) + (double)((u64)cfg_.film.on << 42) +
+                            (double)((u64)cfg_.density_film.on << 43);  // (density-film mode one bit above the film mode's)
         const double lo = t_->allreduce_min(code), hi = t_->allreduce_max(code);
         if (lo != hi) {
             u64 clo = (u64)lo, chi = (u64)hi;
+            if ((clo >> 43) != (chi >> 43))
+                throw Error(strprintf("the ranks disagree on the density-film mode: rank %d has density_film %s (some ranks on, some off)",
+                                      g_.rank, cfg_.density_film.on ? "on" : "off"));
+            clo &= ((u64)1 << 43) - 1;
+            chi &= ((u64)1 << 43) - 1;
             if ((clo >> 42) != (chi >> 42))
                 throw Error(strprintf("the ranks disagree on the film mode: rank %d has film %s (some ranks on, some off)", g_.rank,
                                       cfg_.film.on ? "on" : "off"));
@@ -265,6 +298,17 @@ void Engine::init(const PatternSpec& p) {
             if (!same)
                 throw Error(strprintf("the ranks disagree on the film window: rank %d has %lld x %lld cells at (%lld, %lld)", g_.rank,
                                       (long long)mine[2], (long long)mine[3], (long long)mine[0], (long long)mine[1]));
+        }
+        if (cfg_.density_film.on) {  // (likewise)
+            const i64 mine[2] = {cfg_.density_film.rows, cfg_.density_film.cols};
+            bool same = true;
+            for (i64 v : mine) {
+                const double vlo = t_->allreduce_min((double)v), vhi = t_->allreduce_max((double)v);
+                same = same && vlo == vhi;
+            }
+            if (!same)
+                throw Error(strprintf("the ranks disagree on the density-film blocks: rank %d has blocks of %lld x %lld cells", g_.rank,
+                                      (long long)mine[0], (long long)mine[1]));
         }
     }
     do_init(p);
@@ -386,6 +430,7 @@ void Engine::census_restart(u64 generation) {
     census_host_.clear();
     sig_host_.clear();
     film_host_.clear();
+    density_host_.clear();
     census_start_ = generation;
 }
 
@@ -430,6 +475,54 @@ void Engine::film_clear() {
     if (!cfg_.film.on) throw Error("film_clear(): this engine is not in film mode");
     census_collect();
     census_restart(census_start_ + (u64)(film_host_.size() / (size_t)film_geo_.slot_words()));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Density film (density-film mode's record: density_host_, this rank's maps; gol/density_film.hpp)
+// ---------------------------------------------------------------------------------------------
+
+Engine::DensityFilm Engine::density_film() {
+    if (!cfg_.density_film.on)
+        throw Error("density_film(): this engine is not in density-film mode (EngineConfig::density_film, "
+                    "Simulation(density_film=(block_rows, block_cols)), GOL_DENSITY_FILM=block_rows[,block_cols])");
+    DensityFilm out;
+    out.n = density_film_frames();
+    out.maps.resize(out.n * (size_t)density_geo_.blocks());
+    out.start = density_film_into(out.maps.data(), out.n);
+    return out;
+}
+
+size_t Engine::density_film_frames() {
+    if (!cfg_.density_film.on) throw Error("density_film(): this engine is not in density-film mode");
+    census_collect();
+    return density_host_.size() / (size_t)density_geo_.slot_words();
+}
+
+u64 Engine::density_film_into(u32* out, size_t n) {
+    if (!cfg_.density_film.on) throw Error("density_film(): this engine is not in density-film mode");
+    const size_t slot = (size_t)density_geo_.slot_words(), blocks = (size_t)density_geo_.blocks();
+    if (n * slot != density_host_.size()) throw Error("density_film_into(): the record has changed since density_film_frames()");
+    // The ranks' maps are summed a few at a time (about 1 MiB of slots per round, one map at least): a block's count
+    // is below 2^32, so the two counts of a u64 word add up without a carry between them.
+    const size_t per = std::max<size_t>(1, ((size_t)1 << 17) / slot);
+    std::vector<u64> part;
+    for (size_t at = 0; at < n; at += per) {
+        const size_t m = std::min(per, n - at);
+        const u64* words = density_host_.data() + at * slot;
+        if (t_->size() > 1) {
+            part.assign(words, words + m * slot);
+            sum_series(part, "density_film");
+            words = part.data();
+        }
+        for (size_t i = 0; i < m; ++i) memcpy(out + (at + i) * blocks, words + i * slot, blocks * sizeof(u32));
+    }
+    return census_start_;
+}
+
+void Engine::density_film_clear() {
+    if (!cfg_.density_film.on) throw Error("density_film_clear(): this engine is not in density-film mode");
+    census_collect();
+    census_restart(census_start_ + (u64)(density_host_.size() / (size_t)density_geo_.slot_words()));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -775,7 +868,13 @@ class CpuEngine : public Engine {
             film_host_.resize(film_host_.size() + add, 0);
             film = cpu::FilmOut{&film_geo_, film_host_.data() + (film_host_.size() - add)};
         }
-        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, place, counts, sigs, film);
+        cpu::DensityOut dens;
+        if (cfg_.density_film.on) {  // this rank's counts of every block after each of the k generations
+            const size_t add = (size_t)k * (size_t)density_geo_.slot_words();
+            density_host_.resize(density_host_.size() + add, 0);
+            dens = cpu::DensityOut{&density_geo_, density_host_.data() + (density_host_.size() - add)};
+        }
+        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, place, counts, sigs, film, dens);
         if (res != cur_) std::swap(cur_, oth_);
         if (self_x()) cpu::fill_ghost_cols_wrap(cur_, L_, 0, L_.h);
     }

@@ -62,6 +62,18 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
                                   "at least %zu of them (GOL_FILM_MB; window() reads any rectangle)",
                                   (long long)cfg_.film.rows, (long long)cfg_.film.cols, slot_bytes(), mb, kFilmMinFrames));
     }
+    if (cfg_.density_film.on && cfg_.kernel_depth > hipk::max_density_depth())
+        throw Error(strprintf("density_film: kernel_depth %d exceeds the density kernel's deepest pass, %d generations (GOL_KERNEL_DEPTH)",
+                              cfg_.kernel_depth, hipk::max_density_depth()));
+    if (cfg_.density_film.on) {
+        const long long mb = env_int("GOL_DENSITY_FILM_MB", 64);
+        if (mb < 1 || mb > 2047) throw Error(strprintf("GOL_DENSITY_FILM_MB must be in 1..2047 (got %lld)", mb));
+        film_cap_ = ((size_t)mb << 20) / slot_bytes();
+        if (film_cap_ < kFilmMinFrames)
+            throw Error(strprintf("density_film: a map of %lld x %lld blocks takes %zu bytes, and the %lld MiB map buffer must hold "
+                                  "at least %zu of them (GOL_DENSITY_FILM_MB; density() reads any grid)",
+                                  (long long)density_geo_.grid_rows, (long long)density_geo_.grid_cols, slot_bytes(), mb, kFilmMinFrames));
+    }
     if (rule_ && kernel_ == "auto") kernel_ = "rule";  // (any other name is refused below)
     hipk::ensure_trash();  // before any launch or graph capture
     // Kernel pass depth K (generations per HBM pass) vs halo depth R (generations per
@@ -296,7 +308,8 @@ void HipEngine::set_tile_words(const std::vector<u64>& dense) {
 
 // Census mode: the call's counts go to device slots reserved here (census_begin), in chunks of at most
 // kCensusMaxSlots generations; the kernels find their slot through census_at_ (tile_superstep, launch).
-// Signature mode records the same way, in slots of its own size (slot_words()), and film mode in slots of one frame.
+// Signature mode records the same way, in slots of its own size (slot_words()), film mode in slots of one frame and
+// density-film mode in slots of one map.
 void HipEngine::run(u64 generations) {
     if (!recording() || census_mute_) return run_counted(generations);
     while (generations > 0) {
@@ -324,7 +337,8 @@ void HipEngine::census_begin(u64 generations) {
     if (d_census_) deferred_free_.push_back(d_census_);
     d_census_ = nullptr;
     census_cap_ = 0;
-    const size_t cap = cfg_.film.on ? film_cap_ : std::max<size_t>(n, 1024);  // (film: n <= film_cap_, run()'s chunks)
+    // (film, density film: n <= film_cap_, run()'s chunks)
+    const size_t cap = cfg_.film.on || cfg_.density_film.on ? film_cap_ : std::max<size_t>(n, 1024);
     HIP_CHECK(hipMalloc(&d_census_, cap * slot_bytes()));
     census_cap_ = cap;
     HIP_CHECK(hipMemsetAsync(d_census_, 0, cap * slot_bytes(), s_comp_));
@@ -340,6 +354,11 @@ void HipEngine::census_collect() {
     HIP_CHECK(hipStreamSynchronize(s_comp_));
     if (cfg_.film.on) {  // the frames as they are: this rank's words of the window
         film_host_.insert(film_host_.end(), raw.begin(), raw.end());
+        census_dev_n_ = 0;
+        return;
+    }
+    if (cfg_.density_film.on) {  // the maps as they are: this rank's counts
+        density_host_.insert(density_host_.end(), raw.begin(), raw.end());
         census_dev_n_ = 0;
         return;
     }
@@ -492,7 +511,7 @@ void HipEngine::finish_init() {
     if (!split_ && !dual_ && kern_[0] == "pipe")
         stats_.kernel = strprintf("pipe@%d(%dx%d,%d/CU)", pipe_k_, pipe_cur_.nw - 1, pipe_cur_.l, pipe_cur_.wg);
     if (rule_) {
-        const std::string rk = strprintf(cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", kdepth_);
+        const std::string rk = strprintf(cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", kdepth_);
         stats_.kernel = split_ ? rk + "+boundary:" + rk : rk;
     }
     if (res_) {
@@ -519,7 +538,7 @@ void HipEngine::finish_init() {
                 const PassKernel pk = pass_kernel(kind, ps[j]);
                 c += (j ? "+" : "") + (pk == PK_PIPE   ? strprintf("pipe@%d(%dx%d,%d/CU)", ps[j], g->nw - 1, g->l, g->wg)
                                        : pk == PK_TILE ? strprintf("tile@%d", ps[j])
-                                       : pk == PK_RULE ? strprintf(cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", ps[j])
+                                       : pk == PK_RULE ? strprintf(cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", ps[j])
                                                        : strprintf("temporal@%d", ps[j]));
             }
             tn += strprintf("%scut%d=%s", tn.empty() ? "" : " ", k, c.c_str());
@@ -785,7 +804,13 @@ void HipEngine::launch(int kind, int k, i64 e, const u64* src, u64* dst, hipStre
             pipe_used_ = true;
         } else if (pk == PK_RULE) {
             const hipk::BoardEdges edges{g_.row0, g_.dec.H, g_.word0(), g_.dec.W};
-            if (cfg_.film.on)
+            if (cfg_.density_film.on) {
+                DensityGeo grid = density_geo_;  // (a block larger than the board counts what one of the board's size does)
+                grid.block_rows = std::min(grid.block_rows, g_.dec.H);
+                grid.block_words = std::min(grid.block_words, ceil_div(g_.dec.W, 64));
+                hipk::launch_step_density(k, cfg_.rule, edges, dead_edges(), L_.w, src, dst, p.d, p.waves, sp, grid, census_at_,
+                                          census_at_ ? (i64)(d_census_ + census_cap_ * slot_words() - census_at_) : 0, s);
+            } else if (cfg_.film.on)
                 hipk::launch_step_film(k, cfg_.rule, edges, dead_edges(), L_.w, src, dst, p.d, p.waves, sp,
                                        {film_geo_.r0, film_geo_.rows, film_geo_.w0, film_geo_.fw}, census_at_,
                                        census_at_ ? (i64)(d_census_ + census_cap_ * slot_words() - census_at_) : 0, s);

@@ -311,18 +311,21 @@ class HipEngine : public Engine {
     // The streaming kernel of this engine: step_rule under a rule (rule_), else step_temporal.
     // (in census mode step_census, at its own depths, on either boundary)
     bool depth_ok(int k) const {
+        if (cfg_.density_film.on) return k >= 1 && k <= hipk::max_density_depth(cfg_.rule.nbhd);
         if (cfg_.film.on) return k >= 1 && k <= hipk::max_film_depth(cfg_.rule.nbhd);
         if (cfg_.signature) return k >= 1 && k <= hipk::max_signature_depth(cfg_.rule.nbhd);
         if (cfg_.census) return k >= 1 && k <= hipk::max_census_depth(cfg_.rule.nbhd);
         return rule_ ? hipk::rule_depth_supported(k, cfg_.rule.nbhd) : hipk::step_depth_supported(k);
     }
     int max_depth() const {
+        if (cfg_.density_film.on) return hipk::max_density_depth(cfg_.rule.nbhd);
         if (cfg_.film.on) return hipk::max_film_depth(cfg_.rule.nbhd);
         if (cfg_.signature) return hipk::max_signature_depth(cfg_.rule.nbhd);
         if (cfg_.census) return hipk::max_census_depth(cfg_.rule.nbhd);
         return rule_ ? hipk::max_rule_depth(cfg_.rule.nbhd) : hipk::max_step_depth();
     }
     int blocks_per_cu(int k, u32 flags) const {
+        if (cfg_.density_film.on) return hipk::density_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
         if (cfg_.film.on) return hipk::film_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
         if (cfg_.signature) return hipk::signature_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
         if (cfg_.census) return hipk::census_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
@@ -756,17 +759,20 @@ class HipEngine : public Engine {
     // Film mode uses it with slots of one packed frame (gol/film.hpp: rows x fw words), film_cap_ of them in a buffer
     // of GOL_FILM_MB MiB (default 64, below 2048: a pass's stores index with 32 bits), allocated whole at first use:
     // run() goes in chunks of at most film_cap_ generations, and census_collect() appends the raw frames to film_host_.
+    // Density-film mode likewise, with slots of one map (gol/density_film.hpp: grid_rows x grid_cols u32 in whole u64
+    // words) in a buffer of GOL_DENSITY_FILM_MB MiB, and census_collect() appends the raw maps to density_host_.
     size_t slot_words() const {
+        if (cfg_.density_film.on) return (size_t)density_geo_.slot_words();
         if (cfg_.film.on) return (size_t)film_geo_.slot_words();
         return (size_t)(cfg_.signature ? hipk::kSigSlotWords : hipk::kCensusSlotWords);
     }
     size_t slot_bytes() const { return slot_words() * sizeof(u64); }
     size_t max_slots() const {
-        if (cfg_.film.on) return film_cap_;
+        if (cfg_.film.on || cfg_.density_film.on) return film_cap_;
         return cfg_.signature ? kCensusMaxSlots / 2 : kCensusMaxSlots;
     }
     static constexpr size_t kFilmMinFrames = 8;  // a window whose frames do not fit this often is refused at init
-    size_t film_cap_ = 0;                        // frames the device buffer holds
+    size_t film_cap_ = 0;                        // frames (density-film mode: maps) the device buffer holds
     u64* d_snap_ = nullptr;  // snapshot(): a third board buffer (alloc_bytes_), allocated on first use
     bool res_ = false;  // supersteps run the resident kernel
     int res_kin_ = 0;   // its generations per in-kernel halo exchange

@@ -171,6 +171,7 @@ EngineConfig engine_config(const Options& o, const std::string& backend, int dev
     c.census = o.census;
     c.signature = o.signature;
     if (!o.film.empty()) c.film = parse_film(o.film);
+    if (!o.density_film.empty()) c.density_film = parse_density_film(o.density_film);
     c.tile_waves = (int)env_int("GOL_TILE_WAVES", 8);
     c.tune_tile_waves = getenv("GOL_TILE_WAVES") == nullptr;
     c.transport = (o.transport == "rccl" || o.transport == "p2p") ? "device" : o.transport;
@@ -456,6 +457,10 @@ void write_metrics(const Options& o, Engine& eng, const CliArgs& a, double durat
         f << "  \"film\": [" << s.film.r0 << ", " << s.film.c0 << ", " << s.film.rows << ", " << s.film.cols << "],\n";
     else
         f << "  \"film\": null,\n";
+    if (s.density_film.on)
+        f << "  \"density_film\": [" << s.density_film.rows << ", " << s.density_film.cols << "],\n";
+    else
+        f << "  \"density_film\": null,\n";
     f << "  \"schedule\": \"" << s.schedule << "\",\n";
     f << "  \"autotune\": \"" << s.tuning << "\",\n";
     f << "  \"plan_waves\": " << s.plan_waves << ",\n  \"lane_efficiency\": " << s.lane_efficiency << ",\n";
@@ -507,6 +512,23 @@ CliPattern load_cli_pattern(Options& o) {
     return cp;
 }
 
+// A NumPy .npy version 1.0 file of an (n, rows, cols) C-order array of dtype `descr` ("|u1", "<u4"): GOL_FILM_OUT and
+// GOL_DENSITY_FILM_OUT.  False when the file cannot be written whole.
+bool write_npy(const std::string& path, const char* descr, size_t n, i64 rows, i64 cols, const void* data, size_t bytes) {
+    std::string hdr = strprintf("{'descr': '%s', 'fortran_order': False, 'shape': (%zu, %lld, %lld), }", descr, n, (long long)rows,
+                                (long long)cols);
+    hdr.append(63 - (10 + hdr.size()) % 64, ' ');  // magic, version and length take 10 bytes: data at a multiple of 64
+    hdr.push_back('\n');
+    const unsigned char pre[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(hdr.size() & 0xFF),
+                                   (unsigned char)(hdr.size() >> 8)};
+    FILE* cf = fopen(path.c_str(), "wb");
+    if (!cf) return false;
+    bool ok = fwrite(pre, 1, sizeof(pre), cf) == sizeof(pre) && fwrite(hdr.data(), 1, hdr.size(), cf) == hdr.size() &&
+              (bytes == 0 || fwrite(data, 1, bytes, cf) == bytes);
+    ok = (fclose(cf) == 0) && ok;
+    return ok;
+}
+
 int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const LaunchInfo& li,
              std::shared_ptr<Transport> control) {
     const int rank = control->rank(), P = control->size();
@@ -545,6 +567,16 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
                 throw Error(strprintf("GOL_FILM_OUT: %llu iterations x %lld rows x %lld columns are more than 2^30 bytes of frames; "
                                       "film a smaller window or run fewer iterations",
                                       (unsigned long long)a.iterations, (long long)fr.rows, (long long)fr.cols));
+        }
+        if (!o.density_film_out.empty()) {
+            const DensityBlocks db = parse_density_film(o.density_film);
+            if (db.rows >= 1 && db.cols >= 64 && db.cols % 64 == 0) {  // (else: the engine refuses the blocks)
+                const u64 gr = (u64)ceil_div(dec.H, db.rows), gc = (u64)ceil_div(dec.W, db.cols);
+                if (gr * gc <= (u64)kDensityFilmMaxBlocks && (u64)a.iterations * gr * gc * sizeof(u32) > kFilmOutMaxBytes)
+                    throw Error(strprintf("GOL_DENSITY_FILM_OUT: %llu iterations x %llu x %llu blocks are more than 2^30 bytes of maps; "
+                                          "use larger blocks or run fewer iterations",
+                                          (unsigned long long)a.iterations, (unsigned long long)gr, (unsigned long long)gc));
+            }
         }
         PatternSpec pat = make_pattern(a.pattern, dec, o.seed);
         std::shared_ptr<Transport> t = make_data_transport(control, backend, o, device);
@@ -634,23 +666,20 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
             // the run's frames (collective); rank 0 writes them as .npy version 1.0, and every rank learns whether that worked
             const Engine::Film fm = eng->film();
             u64 ok = 1;
-            if (rank == 0) {
-                std::string hdr = strprintf("{'descr': '|u1', 'fortran_order': False, 'shape': (%zu, %lld, %lld), }", fm.n,
-                                            (long long)ec.film.rows, (long long)ec.film.cols);
-                hdr.append(63 - (10 + hdr.size()) % 64, ' ');  // magic, version and length take 10 bytes: data at a multiple of 64
-                hdr.push_back('\n');
-                const unsigned char pre[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(hdr.size() & 0xFF),
-                                               (unsigned char)(hdr.size() >> 8)};
-                FILE* cf = fopen(o.film_out.c_str(), "wb");
-                ok = cf != nullptr;
-                if (cf) {
-                    ok = fwrite(pre, 1, sizeof(pre), cf) == sizeof(pre) && fwrite(hdr.data(), 1, hdr.size(), cf) == hdr.size() &&
-                         (fm.frames.empty() || fwrite(fm.frames.data(), 1, fm.frames.size(), cf) == fm.frames.size());
-                    ok = (fclose(cf) == 0) && ok;
-                }
-            }
+            if (rank == 0)
+                ok = write_npy(o.film_out, "|u1", fm.n, ec.film.rows, ec.film.cols, fm.frames.data(), fm.frames.size());
             t->broadcast(&ok, sizeof(ok), 0);
             if (!ok) throw Error("GOL_FILM_OUT: cannot write " + o.film_out);
+        }
+        if (!o.density_film_out.empty()) {
+            // the run's maps (collective); rank 0 writes them as .npy version 1.0, and every rank learns whether that worked
+            const Engine::DensityFilm dm = eng->density_film();
+            u64 ok = 1;
+            if (rank == 0)
+                ok = write_npy(o.density_film_out, "<u4", dm.n, eng->density_geo().grid_rows, eng->density_geo().grid_cols,
+                               dm.maps.data(), dm.maps.size() * sizeof(u32));
+            t->broadcast(&ok, sizeof(ok), 0);
+            if (!ok) throw Error("GOL_DENSITY_FILM_OUT: cannot write " + o.density_film_out);
         }
         if (!o.rle_out.empty()) {
             RlePattern out;
@@ -698,6 +727,7 @@ int run_cli(int argc, char** argv) {
         (void)Rule::parse(env_str("GOL_RULE", "B3/S23"));  // (GOL_VERBOSE=1: describe() names the rule)
         (void)parse_boundary(env_str("GOL_BOUNDARY", "torus"));  // GOL_BOUNDARY likewise
         if (!o.film.empty()) (void)parse_film(o.film);           // GOL_FILM likewise
+        if (!o.density_film.empty()) (void)parse_density_film(o.density_film);  // GOL_DENSITY_FILM likewise
         // GOL_PATTERN_FILE likewise: an unreadable file, or one whose rule GOL_RULE contradicts, ends the job here
         const CliPattern cp = load_cli_pattern(o);
         LaunchInfo li = detect_launch(o);

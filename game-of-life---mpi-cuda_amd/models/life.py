@@ -85,6 +85,14 @@ class Simulation:
                   for every rule, neighbourhood and either boundary (generic-kernel speed, B3/S23 included; passes of at
                   most ``max_film_depth`` generations, eager launches; the frames wait in a device buffer of GOL_FILM_MB
                   MiB, default 64); without ``census``, ``signature``, ``compat``, ``subtiles=2`` or the specialised kernels.
+    density_film: density-film mode (default off; GOL_DENSITY_FILM=block_rows[,block_cols]): ``(block_rows, block_cols)``, or
+                  one int for square blocks, :meth:`density`'s block shape (``block_cols`` a multiple of 64; at most 2^20
+                  blocks).  Every generation :meth:`step` computes also yields the density map of the whole board in that
+                  generation, read with :meth:`density_film`.  HIP: the density kernel ``step_density`` counts the blocks
+                  inside every pass, for every rule, neighbourhood and either boundary (generic-kernel speed, B3/S23
+                  included; passes of at most ``max_density_depth`` generations, eager launches; the maps wait in a device
+                  buffer of GOL_DENSITY_FILM_MB MiB, default 64); without ``census``, ``signature``, ``film``, ``compat``,
+                  ``subtiles=2`` or the specialised kernels.
     compat:       reproduce the reference's halo quirks (frozen gen-0 halos, P<=2 swap).
     watchdog:     seconds without progress before the job is aborted (0 = off; GOL_WATCHDOG).
     """
@@ -123,6 +131,7 @@ class Simulation:
         census: Optional[bool] = None,
         signature: Optional[bool] = None,
         film=None,
+        density_film=None,
     ):
         self.transport = transport if transport is not None else _gol.SelfTransport()
         P, rank = self.transport.size(), self.transport.rank()
@@ -226,6 +235,51 @@ class Simulation:
                     f"film: a window of {rows} x {cols} cells has more than 2^22 cells; read larger rectangles with window()"
                 )
             cfg.film = film
+        if density_film is None:  # (read per call, as the census mode is)
+            env = os.environ.get("GOL_DENSITY_FILM", "")
+            if env:
+                try:
+                    density_film = tuple(int(v) for v in env.split(","))
+                except ValueError:
+                    density_film = ()
+                if len(density_film) not in (1, 2):
+                    raise ValueError(f"GOL_DENSITY_FILM must be block_rows[,block_cols] (got {env!r})")
+        if density_film is not None:
+            if isinstance(density_film, (int, np.integer)):
+                density_film = (density_film,)
+            density_film = tuple(int(v) for v in density_film)
+            if len(density_film) == 1:
+                density_film = density_film * 2
+            if len(density_film) != 2:
+                raise ValueError(f"density_film must be (block_rows, block_cols) or one int, got {density_film!r}")
+            brows, bcols = density_film
+            H, W = self.decomposition.H, self.decomposition.W
+            if cfg.census or cfg.signature or cfg.film is not None:
+                raise ValueError("density_film with census=True, signature=True or film: one per-generation record per simulation")
+            if compat:
+                raise ValueError("density_film with compat=True: compat mode runs the reference's loop, not the density kernel")
+            if int(subtiles) == 2:
+                raise ValueError("density_film with subtiles=2: the sub-tile halves do not run the density kernel")
+            if self.backend == "hip" and kernel in ("temporal", "tile", "pipe", "resident", "lds"):
+                raise ValueError(f"kernel {kernel!r} counts no density maps: the density kernel runs every pass (use auto or rule)")
+            if self.backend == "hip" and int(kernel_depth) > _gol.max_density_depth():
+                raise ValueError(
+                    f"density_film: kernel_depth {kernel_depth} exceeds the density kernel's deepest pass, "
+                    f"{_gol.max_density_depth()} generations"
+                )
+            if brows < 1:
+                raise ValueError(f"density_film: block_rows must be >= 1 (got {brows})")
+            if bcols < 64 or bcols % 64:
+                raise ValueError(f"density_film: block_cols must be a multiple of 64, the cells of a board word (got {bcols})")
+            if min(brows, H) * min(bcols, -(-W // 64) * 64) > 0xFFFFFFFF:
+                raise ValueError(f"density_film: a block of {brows} x {bcols} cells holds more than 2^32 - 1 cells, its count would not fit")
+            grows, gcols = -(-H // brows), -(-W // bcols)
+            if grows * gcols > _gol.density_film_max_blocks:
+                raise ValueError(
+                    f"density_film: blocks of {brows} x {bcols} cells make a grid of {grows} x {gcols} blocks, more than 2^20 "
+                    "per generation; read finer grids with density()"
+                )
+            cfg.density_film = density_film
         cfg.subtiles = int(subtiles)  # 2 / 0 / -1 auto: two sub-tiles per rank on two streams (HIP, 1-D)
         cfg.run_hint = int(run_hint)  # generations of the runs to come: one replay graph covers them
         cfg.rows_per_wave = rows_per_wave
@@ -351,6 +405,25 @@ class Simulation:
         if self.config.film is None:
             raise ValueError("film_clear() needs a simulation built with film=(r0, c0, rows, cols) (or GOL_FILM)")
         self.engine.film_clear()
+
+    def density_film(self):
+        """``(start, maps)``: ``maps[i]`` is what ``density(block_rows, block_cols)`` would return at generation
+        ``start + 1 + i``, a ``(n, grid_rows, grid_cols)`` uint32 array with one map per generation computed since the
+        record was cleared (by :meth:`init`, :meth:`load_rle`, :meth:`restore` or :meth:`density_film_clear`;
+        :meth:`stamp` and :meth:`set_board` leave it running).  Collective; every rank gets the same array
+        (:func:`ops.numpy_density_film` is its oracle).  Needs ``density_film=(block_rows, block_cols)``."""
+        if self.config.density_film is None:
+            raise ValueError("density_film() needs a simulation built with density_film=(block_rows, block_cols) (or GOL_DENSITY_FILM)")
+        start, maps = self.engine.density_film()
+        return int(start), maps
+
+    def density_film_clear(self) -> None:
+        """Forget the recorded maps; the next record starts at the generation reached."""
+        if self.config.density_film is None:
+            raise ValueError(
+                "density_film_clear() needs a simulation built with density_film=(block_rows, block_cols) (or GOL_DENSITY_FILM)"
+            )
+        self.engine.density_film_clear()
 
     def snapshot(self) -> None:
         """Keep a copy of the current board (a third board buffer, allocated on first use) for :meth:`snapshot_diff`."""

@@ -4,6 +4,7 @@ from .bitpack import pack_cells, unpack_words  # noqa: F401
 from .oracle import (  # noqa: F401
     initial_board,
     numpy_census,
+    numpy_density_film,
     numpy_film,
     numpy_signature,
     numpy_signatures,

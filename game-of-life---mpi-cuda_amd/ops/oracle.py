@@ -239,6 +239,27 @@ def numpy_film(board: np.ndarray, rule, gens: int, rect, bounded: bool = False, 
     return (frames, b) if return_board else frames
 
 
+def numpy_density_film(board: np.ndarray, rule, gens: int, blocks, bounded: bool = False, return_board: bool = False):
+    """The density maps of ``board`` after generations ``1 .. gens`` under ``rule`` as a ``(gens, grid_rows, grid_cols)``
+    uint32 array (the oracle of the engines' density-film mode), on the torus or, ``bounded``, on a board with dead
+    edges.  ``blocks`` is ``(block_rows, block_cols)`` or one int; a map holds the live cells of every block of that
+    shape, ``ceil(H / block_rows) x ceil(W / block_cols)`` of them, the last of a row or column partial.  One
+    generation of :func:`numpy_step_rule` / :func:`numpy_step_rule_bounded` at a time; the block sums are taken here,
+    with ``np.add.reduceat`` along both axes.  ``return_board`` also returns the last board."""
+    step = numpy_step_rule_bounded if bounded else numpy_step_rule
+    if isinstance(blocks, (int, np.integer)):
+        blocks = (blocks, blocks)
+    br, bc = (int(v) for v in blocks)
+    b = np.asarray(board, dtype=np.uint8)
+    H, W = b.shape
+    ri, ci = np.arange(0, H, br), np.arange(0, W, bc)
+    maps = np.zeros((int(gens), len(ri), len(ci)), dtype=np.uint32)
+    for g in range(int(gens)):
+        b = step(b, rule, 1)
+        maps[g] = np.add.reduceat(np.add.reduceat(b.astype(np.uint32), ri, axis=0), ci, axis=1)
+    return (maps, b) if return_board else maps
+
+
 def torch_step_rule(board, rule, generations: int = 1, device=None):
     """A life-like rule on a torus with torch conv2d (fp32, exact for counts <= 8).  Returns a torch uint8 tensor."""
     import torch
