@@ -20,6 +20,9 @@
 //   wave with that neighbourhood's gates (nbhd_gates.hpp; instantiated in nbhd_rule_kernel.hip, nbhd_bounded_kernel.hip,
 //   nbhd_census_kernel.hip, nbhd_signature_kernel.hip; K = 1..8): the depth and occupancy queries below take the
 //   neighbourhood for that reason.
+//   step_soups<M>     — soup batches (gol/soups.hpp), beside the engine: many independent 64 M x 64 M tori per launch, one
+//                       wave64 per soup with the board in registers, settled inside the kernel (soup_kernel.hip; its host
+//                       API is src/hip/soup_kernel.hpp).
 //   step_lds          — single-generation LDS-tiled variant (tile + ghost words staged in LDS);
 //                       kept as a measured alternative (GOL_KERNEL=lds).
 //   fill_ghost_cols   — x-periodic ghost words for widths that are not a multiple of 64.

@@ -22,6 +22,7 @@
 #include "gol/plan.hpp"
 #include "gol/rle.hpp"
 #include "gol/runtime.hpp"
+#include "gol/soups.hpp"
 #include "gol/transport.hpp"
 
 namespace py = pybind11;
@@ -604,6 +605,128 @@ PYBIND11_MODULE(_gol, m) {
     });
     m.def("write_rle", &write_rle);
     m.def("write_rle_file", &write_rle_file);
+
+    // ---- soup batches ---------------------------------------------------------------------
+    // (what the configuration or a call refuses is a ValueError, like a bad rule string)
+    py::class_<SoupBatch>(m, "SoupBatch")
+        .def(py::init([](i64 n, i64 size, const std::string& rule, const std::string& backend, int device,
+                         const std::string& boundary, bool compat, int workgroup) {
+                 try {
+                     SoupConfig c;
+                     c.n = n;
+                     c.size = size;
+                     c.rule = Rule::parse(rule);
+                     c.backend = backend;
+                     c.device = device;
+                     c.boundary = boundary;
+                     c.compat = compat;
+                     c.workgroup = workgroup;
+                     return SoupBatch::create(c);
+                 } catch (const Error& e) {
+                     throw py::value_error(e.what());
+                 }
+             }),
+             py::arg("n"), py::arg("size") = 64, py::arg("rule") = "B3/S23", py::arg("backend") = "hip", py::arg("device") = 0,
+             py::arg("boundary") = "torus", py::arg("compat") = false, py::arg("workgroup") = 0)
+        .def_property_readonly("n", &SoupBatch::n)
+        .def_property_readonly("size", &SoupBatch::size)
+        .def("init_seed",
+             [](SoupBatch& b, u64 seed) {
+                 py::gil_scoped_release r;
+                 b.init_seed(seed);
+             })
+        .def("init_boards",
+             [](SoupBatch& b, py::array_t<u8, py::array::c_style | py::array::forcecast> cells) {
+                 const i64 S = b.size(), M = b.m();
+                 if (cells.ndim() != 3 || cells.shape(0) != b.n() || cells.shape(1) != S || cells.shape(2) != S)
+                     throw py::value_error(strprintf("soups: the boards are not a (%lld, %lld, %lld) array", (long long)b.n(),
+                                                     (long long)S, (long long)S));
+                 const u8* p = cells.data();
+                 const i64 rows = b.n() * S;
+                 std::vector<u64> words((size_t)(rows * M));
+                 int bad = -1;
+                 {
+                     py::gil_scoped_release r;
+                     for (i64 row = 0; row < rows && bad < 0; ++row)
+                         for (i64 j = 0; j < M; ++j) {
+                             u64 v = 0;
+                             for (int k = 0; k < 64; ++k) {
+                                 const u8 c = p[(size_t)(row * S + 64 * j + k)];
+                                 if (c > 1) bad = c;
+                                 v |= (u64)(c & 1u) << k;
+                             }
+                             words[(size_t)(row * M + j)] = v;
+                         }
+                     if (bad < 0) b.init_words(words.data());
+                 }
+                 if (bad >= 0) throw py::value_error(strprintf("soups: a board cell is %d, not 0 or 1", bad));
+             })
+        .def("step",
+             [](SoupBatch& b, u64 g) {
+                 py::gil_scoped_release r;
+                 b.step(g);
+             })
+        .def(
+            "settle",
+            [](SoupBatch& b, i64 max_gens, bool transient, i64 chunk) {
+                if (max_gens < 0) throw py::value_error(strprintf("soups: max_gens = %lld is negative", (long long)max_gens));
+                try {
+                    py::gil_scoped_release r;
+                    b.settle((u64)max_gens, transient, chunk);
+                } catch (const Error& e) {
+                    throw py::value_error(e.what());
+                }
+            },
+            py::arg("max_gens"), py::arg("transient") = false, py::arg("chunk") = kSoupDefaultChunk)
+        // (period uint32, transient int64, generation uint32, population uint32)
+        .def("records",
+             [](SoupBatch& b) {
+                 std::vector<SoupRecord> rec;
+                 {
+                     py::gil_scoped_release r;
+                     rec = b.records();
+                 }
+                 const py::ssize_t n = (py::ssize_t)rec.size();
+                 py::array_t<u32> period(n), generation(n), population(n);
+                 py::array_t<i64> transient(n);
+                 for (py::ssize_t i = 0; i < n; ++i) {
+                     period.mutable_at(i) = rec[(size_t)i].period;
+                     transient.mutable_at(i) = rec[(size_t)i].transient;
+                     generation.mutable_at(i) = rec[(size_t)i].generation;
+                     population.mutable_at(i) = rec[(size_t)i].population;
+                 }
+                 return py::make_tuple(period, transient, generation, population);
+             })
+        .def("boards",
+             [](SoupBatch& b, const std::vector<i64>& idx) {
+                 std::vector<u8> cells;
+                 try {
+                     py::gil_scoped_release r;
+                     cells = b.boards(idx);
+                 } catch (const Error& e) {
+                     throw py::value_error(e.what());
+                 }
+                 py::array_t<u8> a({(py::ssize_t)idx.size(), (py::ssize_t)b.size(), (py::ssize_t)b.size()});
+                 std::memcpy(a.mutable_data(), cells.data(), cells.size());
+                 return a;
+             })
+        .def("synchronize",
+             [](SoupBatch& b) {
+                 py::gil_scoped_release r;
+                 b.synchronize();
+             })
+        .def("stats", [](const SoupBatch& b) {
+            const SoupStats s = b.stats();
+            py::dict d;
+            d["kernel"] = s.kernel;
+            d["backend"] = s.backend;
+            d["rule"] = s.rule;
+            d["launches"] = s.launches;
+            d["settled"] = s.settled;
+            d["reached"] = s.reached;
+            d["workgroup"] = s.workgroup;
+            return d;
+        });
 
     // ---- I/O + CLI ------------------------------------------------------------------------
     m.def("dump_filename", &io::dump_filename);

@@ -27,6 +27,15 @@ __device__ __forceinline__ u32 dpp_next(u32 v) {
     return (u32)__builtin_amdgcn_mov_dpp((int)v, 0x130 /*wave_shl:1*/, 0xF, 0xF, true);
 }
 
+// lane i <- lane i-1, lane 0 <- lane 63: the wave as a ring (step_soups: a 64-row-group torus per wave)
+__device__ __forceinline__ u32 dpp_ring_prev(u32 v) {
+    return (u32)__builtin_amdgcn_mov_dpp((int)v, 0x13C /*wave_ror:1*/, 0xF, 0xF, false);
+}
+// lane i <- lane i+1, lane 63 <- lane 0
+__device__ __forceinline__ u32 dpp_ring_next(u32 v) {
+    return (u32)__builtin_amdgcn_mov_dpp((int)v, 0x134 /*wave_rol:1*/, 0xF, 0xF, false);
+}
+
 __device__ __forceinline__ u32 rule32(u32 a0, u32 a1, u32 b0, u32 b1, u32 c0, u32 c1, u32 x) {
     const u32 x0 = b3<kLutXor3>(a0, b0, c0);
     const u32 cy = b3<kLutMaj>(a0, b0, c0);

@@ -20,6 +20,7 @@
 #include "gol/io.hpp"
 #include "gol/pattern.hpp"
 #include "gol/rle.hpp"
+#include "gol/soups.hpp"
 #include "gol/trace.hpp"
 
 namespace gol {
@@ -529,6 +530,54 @@ bool write_npy(const std::string& path, const char* descr, size_t n, i64 rows, i
     return ok;
 }
 
+// GOL_SOUPS=N: a soup batch (soups.hpp) on one rank instead of an engine run: N tori of side worldSize from pattern 5,
+// settled up to `iterations` generations.  One line on stdout; GOL_SOUPS_OUT gets one line per soup.
+int run_soups(const CliArgs& a, const Options& o, const LaunchInfo& li) {
+    const long long n = env_int("GOL_SOUPS", 0);
+    if (a.pattern != 5) throw Error(strprintf("GOL_SOUPS runs random soups (pattern 5), not pattern %u", a.pattern));
+    if (li.mode != "single")
+        throw Error(strprintf("GOL_SOUPS runs on one rank, not under a %s launch of %d ranks", li.mode.c_str(), li.size));
+    const std::string boundary = o.boundary.empty() ? env_str("GOL_BOUNDARY", "torus") : o.boundary;
+    if (parse_boundary(boundary) != Boundary::Torus) throw Error("GOL_SOUPS with GOL_BOUNDARY=" + boundary + ": a soup is a torus");
+    if (o.compat) throw Error("GOL_SOUPS with GOL_COMPAT=reference: a soup is a correct torus");
+    if (o.census) throw Error("GOL_SOUPS with census mode (GOL_CENSUS / GOL_CENSUS_OUT): a soup batch records no series");
+    if (o.signature) throw Error("GOL_SOUPS with signature mode (GOL_SIGNATURE / GOL_SIGNATURE_OUT): a soup batch compares boards");
+    if (!o.film.empty()) throw Error("GOL_SOUPS with film mode (GOL_FILM): a soup batch films nothing");
+    if (!o.density_film.empty()) throw Error("GOL_SOUPS with density-film mode (GOL_DENSITY_FILM): a soup batch films nothing");
+    SoupConfig c;
+    c.n = n;
+    c.size = (i64)a.world_size;
+    c.rule = Rule::parse(o.rule.empty() ? env_str("GOL_RULE", "B3/S23") : o.rule);
+    if (o.backend != "auto" && o.backend != "hip" && o.backend != "cpu")
+        throw Error("GOL_BACKEND must be auto, hip or cpu (got " + o.backend + ")");
+    c.backend = o.backend == "auto" ? (hip_device_count() > 0 ? "hip" : "cpu") : o.backend;
+    const bool transient = env_flag("GOL_SOUPS_TRANSIENT", false);
+    const long long chunk = env_int("GOL_SOUPS_CHUNK", kSoupDefaultChunk);
+    const std::string out = env_str("GOL_SOUPS_OUT", "");
+    std::unique_ptr<SoupBatch> sb = SoupBatch::create(c);
+    if (o.verbose) fprintf(stderr, "[gol] soups: %lld x %u^2, rule %s, backend %s\n", n, a.world_size, c.rule.str().c_str(), c.backend.c_str());
+    sb->init_seed(o.seed);
+    const double t0 = wtime();
+    sb->settle((u64)a.iterations, transient, chunk);
+    const std::vector<SoupRecord> rec = sb->records();
+    const double duration = wtime() - t0;
+    printf("soups %lld settled %llu of %lld in %.6f s\n", n, (unsigned long long)sb->stats().settled, n, duration);
+    fflush(stdout);
+    if (!out.empty()) {
+        FILE* cf = fopen(out.c_str(), "w");
+        bool ok = cf != nullptr;
+        if (cf) {
+            ok = fputs("soup,period,transient,generation,population\n", cf) >= 0;
+            for (size_t i = 0; i < rec.size() && ok; ++i)
+                ok = fprintf(cf, "%zu,%u,%lld,%u,%u\n", i, rec[i].period, (long long)rec[i].transient, rec[i].generation,
+                             rec[i].population) > 0;
+            ok = (fclose(cf) == 0) && ok;
+        }
+        if (!ok) throw Error("GOL_SOUPS_OUT: cannot write " + out);
+    }
+    return 0;
+}
+
 int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const LaunchInfo& li,
              std::shared_ptr<Transport> control) {
     const int rank = control->rank(), P = control->size();
@@ -731,6 +780,7 @@ int run_cli(int argc, char** argv) {
         // GOL_PATTERN_FILE likewise: an unreadable file, or one whose rule GOL_RULE contradicts, ends the job here
         const CliPattern cp = load_cli_pattern(o);
         LaunchInfo li = detect_launch(o);
+        if (getenv("GOL_SOUPS") && *getenv("GOL_SOUPS")) return run_soups(a, o, li);  // (unset: nothing changes)
         if (li.mode == "threads") {
             auto group = make_thread_group(li.size);
             std::vector<int> status((size_t)li.size, 0);

@@ -1,0 +1,92 @@
+"""Soup batches: many small random tori ("soups") per launch, each run until it settles.
+
+:class:`SoupBatch` drives a native ``_gol.SoupBatch`` (HIP: the ``step_soups`` kernel, one wave64 per soup with the board
+in registers; CPU: the same per-soup program on packed words).  It is not a :class:`Simulation`: no engine, plan or
+autotune, one rank, Moore rules on the torus.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional, Sequence
+
+import numpy as np
+
+from .._native import _gol
+
+SIZES = (64, 128, 256)
+MAX_SOUPS = 1 << 20
+
+
+class SoupResult(NamedTuple):
+    """What :meth:`SoupBatch.settle` returns, one entry per soup."""
+
+    period: np.ndarray      # uint32; 0: not settled by ``generation``
+    transient: np.ndarray   # int64; -1: not computed (no ``transient=True``, or not settled)
+    generation: np.ndarray  # uint32; the generation of the hit, or ``max_gens``
+    population: np.ndarray  # uint32; live cells at ``generation``
+
+
+class SoupBatch:
+    """``n`` independent square tori of side ``size`` (64, 128 or 256) under one Moore rule.
+
+    Soup ``i`` starts as ``ops.random_board(size, size, (seed + i) mod 2**64)`` (pattern 5), or from a caller's array
+    (:meth:`from_boards`).  :meth:`settle` runs Brent's search with exact board comparison (``ops.numpy_soup_settle`` states
+    it) on every soup at once; :meth:`step` is the plain stepper.  ``V`` / ``H`` rules, ``boundary="dead"`` and
+    ``compat=True`` are refused.  ``backend``: ``"hip"`` or ``"cpu"``; both give identical results.
+    """
+
+    def __init__(self, n: int, size: int = 64, rule: str = "B3/S23", backend: str = "hip", seed: int = 0, device: int = 0, *,
+                 boundary: str = "torus", compat: bool = False, workgroup: int = 0, _boards=None):
+        n, size = int(n), int(size)
+        if size not in SIZES:
+            raise ValueError(f"soups: size {size} is not supported (a soup is a square torus of side 64, 128 or 256)")
+        if not 1 <= n <= MAX_SOUPS:
+            raise ValueError(f"soups: n = {n} is outside 1 .. 2^20")
+        self._native = _gol.SoupBatch(n, size, str(rule), str(backend), int(device), str(boundary), bool(compat), int(workgroup))
+        self.n, self.size, self.backend = n, size, str(backend)
+        if _boards is None:
+            self._native.init_seed(int(seed) & ((1 << 64) - 1))
+        else:
+            self._native.init_boards(_boards)
+
+    @classmethod
+    def from_boards(cls, boards, rule: str = "B3/S23", backend: str = "hip", device: int = 0, **kw) -> "SoupBatch":
+        """A batch of the ``(n, S, S)`` 0/1 array ``boards``, one soup per board."""
+        b = np.asarray(boards)
+        if b.ndim != 3 or b.shape[1] != b.shape[2]:
+            raise ValueError(f"soups: boards of shape {b.shape} are not an (n, S, S) array")
+        bad = (b != 0) & (b != 1)
+        if bad.any():
+            raise ValueError(f"soups: a board cell is {b[bad].flat[0].item()!r}, not 0 or 1")
+        return cls(b.shape[0], b.shape[1], rule, backend, 0, device, _boards=np.ascontiguousarray(b, dtype=np.uint8), **kw)
+
+    def step(self, generations: int = 1) -> "SoupBatch":
+        """``generations`` steps of every soup, with no comparison.  Refused once :meth:`settle` has begun a search (the
+        settled soups stand at different generations).  A search begun after stepping counts its saves from there."""
+        if int(generations) < 0:
+            raise ValueError(f"soups: step({generations}) is negative")
+        self._native.step(int(generations))
+        return self
+
+    def settle(self, max_gens: int, transient: bool = False, chunk: int = 4096) -> SoupResult:
+        """Run every soup that has not settled until it does or stands at generation ``max_gens``; ``transient`` also finds
+        the exact transient of every settled soup.  One launch advances a soup by at most ``chunk`` generations; the
+        result depends neither on ``chunk`` nor on how ``max_gens`` was reached over several calls."""
+        self._native.settle(int(max_gens), bool(transient), int(chunk))
+        return self.records()
+
+    def synchronize(self) -> None:
+        """Wait for the launches of :meth:`step` (HIP); every other call returns finished work."""
+        self._native.synchronize()
+
+    def records(self) -> SoupResult:
+        return SoupResult(*self._native.records())
+
+    def boards(self, indices: Optional[Sequence[int]] = None) -> np.ndarray:
+        """The boards of the soups ``indices`` (default: all) as a ``(k, S, S)`` uint8 array; only they leave the device."""
+        idx = list(range(self.n)) if indices is None else [int(i) for i in indices]
+        return self._native.boards(idx)
+
+    def stats(self) -> dict:
+        """``kernel`` (``soups@64``, ``soups@128``, ``soups@256``; ``:rule`` appended for the generic variant), ``launches``,
+        ``settled``, ``reached`` (the generation of the unsettled soups), ``backend``, ``rule``, ``workgroup``."""
+        return dict(self._native.stats())

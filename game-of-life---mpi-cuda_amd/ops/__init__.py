@@ -8,6 +8,7 @@ from .oracle import (  # noqa: F401
     numpy_film,
     numpy_signature,
     numpy_signatures,
+    numpy_soup_settle,
     numpy_step,
     numpy_step_rule,
     numpy_step_rule_bounded,

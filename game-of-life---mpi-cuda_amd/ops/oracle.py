@@ -7,6 +7,8 @@
   with a rule parser of their own (independent of the native one).
 * :func:`numpy_step_rule_bounded` — a life-like rule on a bounded board (dead cells beyond the edges), from a
   zero-padded neighbour count, written without the torus oracle.
+* :func:`numpy_soup_settle` — one soup of a soup batch: Brent's search with exact board comparison, and the exact
+  transient, on :func:`numpy_step_rule`.
 * :func:`quirk_model` — the reference's actual behaviour (survey Q1-Q3): every rank steps its tile
   with x-wrap and CONSTANT ghost rows taken from the generation-0 boards, with the P <= 2 swap.
 * :func:`initial_board` — pattern placement mirror (patterns 0-5) computed in Python, including the
@@ -258,6 +260,37 @@ def numpy_density_film(board: np.ndarray, rule, gens: int, blocks, bounded: bool
         b = step(b, rule, 1)
         maps[g] = np.add.reduceat(np.add.reduceat(b.astype(np.uint32), ri, axis=0), ci, axis=1)
     return (maps, b) if return_board else maps
+
+
+def numpy_soup_settle(board: np.ndarray, rule, max_gens: int, transient: bool = False):
+    """One soup of a soup batch (``SoupBatch.settle``), byte per cell on :func:`numpy_step_rule`: Brent's search with exact
+    board comparison.  The soup keeps a copy of its board saved at generation ``s`` and a window ``w``, at first ``s = 0``
+    and ``w = 1``.  After each step to generation ``g``: a board equal to the copy means settled, ``period = g - s``,
+    ``generation = g``, and the soup stops; otherwise ``g - s == w`` saves the board, ``s = g``, ``w *= 2`` (the saves fall at
+    generations 0, 1, 3, 7, ...).  A soup that reaches ``max_gens`` without a hit has ``period = 0`` and ``generation =
+    max_gens``.  ``population`` is the live cells of the board at ``generation``.  ``transient`` (for a settled soup): two
+    copies restart from the initial board, one is advanced ``period`` generations, and both are stepped until they are
+    equal; the number of steps is the transient (-1 without the option or for an unsettled soup).
+    Returns ``(period, transient, generation, population, final_board)``."""
+    init = np.asarray(board, dtype=np.uint8)
+    b, saved = init, init
+    g, s, w, period = 0, 0, 1, 0
+    while g < int(max_gens):
+        b = numpy_step_rule(b, rule, 1)
+        g += 1
+        if np.array_equal(b, saved):
+            period = g - s
+            break
+        if g - s == w:
+            saved, s, w = b, g, 2 * w
+    tr = -1
+    if transient and period:
+        x, y = init, numpy_step_rule(init, rule, period)
+        tr = 0
+        while not np.array_equal(x, y):
+            x, y = numpy_step_rule(x, rule, 1), numpy_step_rule(y, rule, 1)
+            tr += 1
+    return period, tr, g, int(b.sum(dtype=np.uint64)), b
 
 
 def torch_step_rule(board, rule, generations: int = 1, device=None):
