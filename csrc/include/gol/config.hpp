@@ -64,6 +64,9 @@ struct Options {
                                         // whole board in every generation of the run
     std::string density_film_out = "";  // GOL_DENSITY_FILM_OUT  needs GOL_DENSITY_FILM; rank 0 writes the maps there as a NumPy
                                         // .npy file (uint32, shape (iterations, grid_rows, grid_cols))
+    bool envelope = false;          // GOL_ENVELOPE  envelope mode: every cell that was ever alive during the run (implied by
+                                    // GOL_ENVELOPE_OUT)
+    std::string envelope_out = "";  // GOL_ENVELOPE_OUT  rank 0 writes the global envelope after the run as RLE (<= 2^26 cells)
     std::string rle_out = "";       // GOL_RLE_OUT  rank 0 writes the final global board as RLE (<= 2^26 cells)
     std::string rule = "";          // the run's rule when GOL_PATTERN_FILE names one and GOL_RULE is unset
     std::string boundary = "";      // the run's boundary when GOL_PATTERN_FILE names a topology and GOL_BOUNDARY is

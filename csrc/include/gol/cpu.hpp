@@ -66,7 +66,10 @@ struct DensityOut {
 };
 u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule = Rule(), const Edges& edges = Edges(),
                u64* counts = nullptr, u64* sigs = nullptr, const FilmOut& film = FilmOut(),
-               const DensityOut& density = DensityOut());
+               const DensityOut& density = DensityOut(), u64* envelope = nullptr);
+// envelope (envelope mode; nullptr: none): a buffer in layout L; after every generation the tile's own cells (rows
+// [0, h), words [0, nw), storage mask on the last word) are ORed into it.  envelope_or does that for one board.
+void envelope_or(u64* envelope, const u64* board, const Layout& L);
 
 // x-periodic ghost words (and tail ghost bits) for rows [r_lo, r_hi).
 void fill_ghost_cols_wrap(u64* buf, const Layout& L, i64 r_lo, i64 r_hi);

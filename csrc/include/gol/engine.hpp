@@ -75,6 +75,10 @@ struct EngineConfig {
                                       // computes also yields the density(block_rows, block_cols) grid of the global
                                       // board (Engine::density_film).  HIP: step_density counts it inside every pass.
                                       // Not together with census, signature or film
+    bool envelope = false;            // envelope mode (GOL_ENVELOPE): the engine keeps the OR of every generation of the
+                                      // board since the last reset, one bit per cell (Engine::envelope_*).  HIP: a third
+                                      // board-sized buffer, and step_envelope ORs into it inside every pass.  Not
+                                      // together with census, signature, film or density_film
     int tile_waves = 8;               // tile kernel: waves per workgroup (4, 8, 16)
     bool tune_tile_waves = true;      // GOL_KERNEL=auto may also try 8 waves (false: GOL_TILE_WAVES set)
     std::string transport = "auto";   // auto | device | host  (host = stage halos through host memory)
@@ -127,6 +131,8 @@ struct EngineStats {
     bool signature = false;    // signature mode
     FilmRect film;             // film mode: the window (on = false: off)
     DensityBlocks density_film;  // density-film mode: the blocks (on = false: off)
+    bool envelope = false;     // envelope mode
+    u64 envelope_start = 0;    // envelope mode: the generation of the envelope's last reset
     std::string schedule;      // superstep schedule: local (no neighbours) | split | full
     std::string tuning;        // init-time measurements behind the auto choices (HIP)
     bool registered = false;   // HIP + RCCL: the boards are registered with the communicator (zero-copy halos)
@@ -187,9 +193,22 @@ class Engine {
     // differ between the current board and the snapshot; throws, before any communication, without a snapshot.
     void snapshot();
     u64 snapshot_diff();
-    bool recording() const {  // run() keeps a per-generation record
-        return cfg_.census || cfg_.signature || cfg_.film.on || cfg_.density_film.on;
-    }
+    // run() keeps a record made inside the stepping kernel: per generation, or (envelope mode) one OR over them
+    bool recording() const { return cfg_.census || cfg_.signature || cfg_.film.on || cfg_.density_film.on || cfg_.envelope; }
+
+    // ----- envelope (EngineConfig::envelope) -----
+    // E = board(start) | board(start + 1) | ... | board(generation()), cell by cell, with start the generation of the
+    // last reset: init(), set_tile_words() (so a checkpoint restore too) and envelope_clear() make E the current board
+    // and start the generation reached; stamp() is followed by E |= board.  Each rank keeps E for its own tile, in
+    // the board's layout.  The readers are the board's readers run on E: envelope_tile_words() this rank's tile (no
+    // communication), the others collective and the same on every rank.  All throw, before any communication, on an
+    // engine that is not in envelope mode.
+    u64 envelope_start() const;
+    std::vector<u64> envelope_tile_words();
+    std::vector<u8> envelope_window(i64 r0, i64 c0, i64 rows, i64 cols);
+    std::vector<u32> envelope_density(i64 block_rows, i64 block_cols);
+    u64 envelope_population();
+    void envelope_clear();
 
     // ----- film (EngineConfig::film) -----
     // Collective: (start, n, frames): frame i, rows x cols 0/1 bytes at frames[i * rows * cols], is what
@@ -382,6 +401,14 @@ class Engine {
     virtual void snapshot_local() = 0;
     virtual u64 snapshot_diff_local() = 0;
     bool have_snapshot_ = false;
+    // Envelope mode.  envelope_merge_local: E = (reset ? 0 : E) | the tile's own cells of the current board.
+    // view_env_: tile_words(), read_window_local(), density_local() and local_reduce() read E instead of the board
+    // (set for the length of an envelope_* reader).
+    virtual void envelope_merge_local(bool reset) = 0;
+    void envelope_reset();  // start = generation(), E = the current board
+    void need_envelope(const char* what) const;
+    bool view_env_ = false;
+    u64 env_start_ = 0;
 
     Geometry g_;
     EngineConfig cfg_;

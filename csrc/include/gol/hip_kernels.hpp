@@ -168,6 +168,18 @@ int density_blocks_per_cu(int k, u32 flags, bool bounded, Nbhd nbhd = Nbhd::Moor
 void launch_step_density(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src, u64* dst,
                          const LaneDesc* plan, i64 n_waves, const StepParams& p, const DensityGeo& grid, u64* maps,
                          i64 maps_words, hipStream_t s);
+// step_envelope<K> (envelope_kernel.hip): step_rule / step_rule_bounded that also ORs every generation of the pass
+// into the envelope.  `env` is a buffer in the board's own layout (the allocation of src and dst: same pitch, halo
+// and slack rows; device memory; nullptr: touch nothing): after the launch, the envelope word at the offset of a
+// word this launch's store lanes own also holds every cell of that word alive after generation 1 .. k of the pass;
+// no other word of env is read or written.  Plans, StepParams, rows and words of the board read and written, and the
+// argument checks, as launch_step_film.  Depths 1 .. max_envelope_depth().
+int max_envelope_depth(Nbhd nbhd = Nbhd::Moore);
+int envelope_blocks_per_cu(int k, u32 flags, bool bounded, Nbhd nbhd = Nbhd::Moore);
+void launch_step_envelope(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src, u64* dst,
+                          u64* env, const LaneDesc* plan, i64 n_waves, const StepParams& p, hipStream_t s);
+// env = (reset ? 0 : env) | the tile's own cells of `board` (aux_kernels.hip; both buffers in layout L).
+void launch_envelope_merge(u64* env, const u64* board, const Layout& L, bool reset, hipStream_t s);
 // out[0] += the signature of the tile in `buf` at (grow0, gword0) (wrapping; out zeroed by the caller).
 void launch_signature(const u64* buf, const Layout& L, i64 grow0, i64 gword0, u64* out, hipStream_t s);
 // out[0] += the number of cells of the tile that differ between boards a and b (one layout; out zeroed by the caller).

@@ -120,6 +120,10 @@ py::dict stats_dict(const EngineStats& s) {
         d["density_film"] = py::make_tuple(s.density_film.rows, s.density_film.cols);
     else
         d["density_film"] = py::none();
+    if (s.envelope)
+        d["envelope"] = s.envelope_start;
+    else
+        d["envelope"] = py::none();
     d["schedule"] = s.schedule;
     d["kernel_depth"] = s.kernel_depth;
     d["tile_waves"] = s.tile_waves;
@@ -311,6 +315,7 @@ PYBIND11_MODULE(_gol, m) {
                 const py::sequence q = py::reinterpret_borrow<py::sequence>(v);
                 c.film = FilmRect{true, q[0].cast<i64>(), q[1].cast<i64>(), q[2].cast<i64>(), q[3].cast<i64>()};
             })
+        .def_readwrite("envelope", &EngineConfig::envelope)
         // density-film mode: None (off) or the blocks (block_rows, block_cols)
         .def_property(
             "density_film",
@@ -463,6 +468,44 @@ PYBIND11_MODULE(_gol, m) {
                  return py::make_tuple(start, a);
              })
         .def("density_film_clear", &Engine::density_film_clear, py::call_guard<py::gil_scoped_release>())
+        // envelope mode: (start, words), the OR of this rank's tile over generations start .. generation() as tile_words()
+        // returns the board; the board's collective readers on the envelope; the reset
+        .def("envelope",
+             [](Engine& e) {
+                 std::vector<u64> d;
+                 u64 start = 0;
+                 {
+                     py::gil_scoped_release r;
+                     start = e.envelope_start();
+                     d = e.envelope_tile_words();
+                 }
+                 return py::make_tuple(start, words_to_numpy(d, e.layout().h, e.layout().nw));
+             })
+        .def("envelope_window",
+             [](Engine& e, i64 r0, i64 c0, i64 rows, i64 cols) {
+                 std::vector<u8> d;
+                 {
+                     py::gil_scoped_release r;
+                     d = e.envelope_window(r0, c0, rows, cols);
+                 }
+                 py::array_t<u8> a({(py::ssize_t)rows, (py::ssize_t)cols});
+                 memcpy(a.mutable_data(), d.data(), d.size());
+                 return a;
+             })
+        .def("envelope_density",
+             [](Engine& e, i64 block_rows, i64 block_cols) {
+                 std::vector<u32> d;
+                 {
+                     py::gil_scoped_release r;
+                     d = e.envelope_density(block_rows, block_cols);
+                 }
+                 const Decomposition& dec = e.geometry().dec;
+                 py::array_t<u32> a({(py::ssize_t)ceil_div(dec.H, block_rows), (py::ssize_t)ceil_div(dec.W, block_cols)});
+                 memcpy(a.mutable_data(), d.data(), d.size() * sizeof(u32));
+                 return a;
+             })
+        .def("envelope_population", &Engine::envelope_population, py::call_guard<py::gil_scoped_release>())
+        .def("envelope_clear", &Engine::envelope_clear, py::call_guard<py::gil_scoped_release>())
         // any mode (collective): the signature of the current board; a copy of the board, and the cells that differ from it
         .def("signature", &Engine::signature, py::call_guard<py::gil_scoped_release>())
         .def("snapshot", &Engine::snapshot, py::call_guard<py::gil_scoped_release>())
@@ -753,6 +796,7 @@ PYBIND11_MODULE(_gol, m) {
     m.def("max_census_depth", []() { return hipk::max_census_depth(); });  // deepest pass of the census kernel
     m.def("max_signature_depth", []() { return hipk::max_signature_depth(); });  // ... of the signature kernel
     m.def("max_film_depth", []() { return hipk::max_film_depth(); });            // ... of the film kernel
+    m.def("max_envelope_depth", []() { return hipk::max_envelope_depth(); });    // ... of the envelope kernel
     m.def("max_density_depth", []() { return hipk::max_density_depth(); });      // ... of the density kernel
     m.attr("density_film_max_blocks") = kDensityFilmMaxBlocks;                   // blocks of the finest grid density-film mode takes
     m.attr("film_max_cells") = kFilmMaxCells;                                    // cells of the largest window film mode takes

@@ -98,6 +98,8 @@ Options options_from_env() {
     o.density_film_out = env_str("GOL_DENSITY_FILM_OUT", "");
     if (!o.density_film_out.empty() && o.density_film.empty())
         throw Error("GOL_DENSITY_FILM_OUT needs GOL_DENSITY_FILM=block_rows[,block_cols] (the blocks of the maps)");
+    o.envelope_out = env_str("GOL_ENVELOPE_OUT", "");
+    o.envelope = env_int("GOL_ENVELOPE", 0) != 0 || !o.envelope_out.empty();
     if (o.halo_depth < 0 || o.halo_depth > 128) throw Error("GOL_HALO_DEPTH must be in 1..128 (0 = auto)");
     if (o.kernel_depth < 0 || o.kernel_depth > 64) throw Error("GOL_KERNEL_DEPTH must be in 1..64 (0 = auto)");
     return o;

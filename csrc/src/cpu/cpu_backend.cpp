@@ -203,8 +203,16 @@ void density_map(const u64* buf, const Layout& L, const Edges& edges, const Dens
 
 }  // namespace
 
+void envelope_or(u64* envelope, const u64* board, const Layout& L) {
+    for (i64 r = 0; r < L.h; ++r) {
+        const u64* row = board + L.index(r, 0);
+        u64* erow = envelope + L.index(r, 0);
+        for (i64 c = 0; c < L.nw; ++c) erow[c] |= row[c] & storage_mask(c, L.w);
+    }
+}
+
 u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges, u64* counts, u64* sigs,
-               const FilmOut& film, const DensityOut& density) {
+               const FilmOut& film, const DensityOut& density, u64* envelope) {
     if (k < 1 || k > L.R) throw Error(strprintf("superstep depth %d outside 1..%d", k, L.R));
     u64* src = a;
     u64* dst = b;
@@ -216,6 +224,7 @@ u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const E
         if (sigs) sigs[g] += signature(dst, L, edges.row0, edges.word0);
         if (film.frames) film_frame(dst, L, edges, *film.geo, film.frames + (i64)g * film.geo->slot_words());
         if (density.maps) density_map(dst, L, edges, *density.geo, density.maps + (i64)g * density.geo->slot_words());
+        if (envelope) envelope_or(envelope, dst, L);
         std::swap(src, dst);
     }
     return src;

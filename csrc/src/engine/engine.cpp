@@ -101,6 +101,18 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
                                   (long long)ceil_div(g_.dec.W, b.cols)));
         density_geo_ = DensityGeo(b, g_.dec.H, g_.dec.W);
     }
+    if (cfg_.envelope) {
+        if (cfg_.census) throw Error("envelope together with census: one in-kernel record per engine (envelope mode keeps one OR, not counts)");
+        if (cfg_.signature) throw Error("envelope together with signature: one in-kernel record per engine (envelope mode keeps one OR, not hashes)");
+        if (cfg_.film.on) throw Error("envelope together with film: one in-kernel record per engine (envelope mode keeps one OR, not frames)");
+        if (cfg_.density_film.on) throw Error("envelope together with density_film: one in-kernel record per engine (envelope mode keeps one OR, not maps)");
+        if (cfg_.compat) throw Error("envelope with GOL_COMPAT=reference: compat mode runs the reference's loop, not the envelope kernel");
+        if (cfg_.subtiles == 2) throw Error("two sub-tiles per rank (GOL_SUBTILES=2) do not run the envelope kernel");
+        if (cfg_.backend == "hip")
+            for (const char* k : {"temporal", "tile", "pipe", "resident", "lds"})
+                if (cfg_.kernel == k)
+                    throw Error("kernel '" + cfg_.kernel + "' keeps no envelope: the envelope kernel runs every pass (use kernel auto or rule)");
+    }
     if (t_->size() != g_.dec.P || t_->rank() != g_.rank)
         throw Error(strprintf("transport (rank %d of %d) does not match the geometry (rank %d of %d)", t_->rank(),
                               t_->size(), g_.rank, g_.dec.P));
@@ -146,6 +158,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     stats_.signature = cfg_.signature;
     stats_.film = cfg_.film;
     stats_.density_film = cfg_.density_film;
+    stats_.envelope = cfg_.envelope;
     std::string f = env_str("GOL_FAULT", "");
     if (!f.empty()) {
         int fr = -1;
@@ -250,6 +263,7 @@ void Engine::init(const PatternSpec& p) {
     stats_.signature = cfg_.signature;
     stats_.film = cfg_.film;
     stats_.density_film = cfg_.density_film;
+    stats_.envelope = cfg_.envelope;
     census_restart(0);
     have_snapshot_ = false;
     if (t_->size() > 1) {
@@ -260,10 +274,16 @@ void Engine::init(const PatternSpec& p) {
         // (film mode one bit above the signature mode's; the window's four numbers are agreed after the modes)
         const double code = (double)cfg_.rule.code() + (double)((u64)cfg_.boundary << 32) + (double)((u64)cfg_.census << 40) +
                             (double)((u64)cfg_.signature << 41) + (double)((u64)cfg_.film.on << 42) +
-                            (double)((u64)cfg_.density_film.on << 43);  // (density-film mode one bit above the film mode's)
+                            (double)((u64)cfg_.density_film.on << 43) +  // (density-film mode one bit above the film mode's)
+                            (double)((u64)cfg_.envelope << 44);          // (envelope mode one bit above that)
         const double lo = t_->allreduce_min(code), hi = t_->allreduce_max(code);
         if (lo != hi) {
             u64 clo = (u64)lo, chi = (u64)hi;
+            if ((clo >> 44) != (chi >> 44))
+                throw Error(strprintf("the ranks disagree on the envelope mode: rank %d has envelope %s (some ranks on, some off)",
+                                      g_.rank, cfg_.envelope ? "on" : "off"));
+            clo &= ((u64)1 << 44) - 1;
+            chi &= ((u64)1 << 44) - 1;
             if ((clo >> 43) != (chi >> 43))
                 throw Error(strprintf("the ranks disagree on the density-film mode: rank %d has density_film %s (some ranks on, some off)",
                                       g_.rank, cfg_.density_film.on ? "on" : "off"));
@@ -312,6 +332,7 @@ void Engine::init(const PatternSpec& p) {
         }
     }
     do_init(p);
+    if (cfg_.envelope) envelope_reset();  // (after the backend's init-time timing, which leaves the envelope alone)
     if (cfg_.compat) setup_compat();
     if (wd_) wd_->enable_probe();
 }
@@ -526,6 +547,63 @@ void Engine::density_film_clear() {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Envelope (envelope mode: the backends keep E beside the board; the board's readers run on it)
+// ---------------------------------------------------------------------------------------------
+
+void Engine::need_envelope(const char* what) const {
+    if (!cfg_.envelope)
+        throw Error(std::string(what) + ": this engine is not in envelope mode (EngineConfig::envelope, Simulation(envelope=True), GOL_ENVELOPE=1)");
+}
+
+void Engine::envelope_reset() {
+    env_start_ = gen_;
+    stats_.envelope_start = env_start_;
+    envelope_merge_local(true);
+}
+
+namespace {
+struct ViewEnvelope {  // the board's readers read the envelope while this lives
+    explicit ViewEnvelope(bool& f) : f_(f) { f_ = true; }
+    ~ViewEnvelope() { f_ = false; }
+    bool& f_;
+};
+}  // namespace
+
+u64 Engine::envelope_start() const {
+    need_envelope("envelope()");
+    return env_start_;
+}
+
+std::vector<u64> Engine::envelope_tile_words() {
+    need_envelope("envelope()");
+    ViewEnvelope v(view_env_);
+    return tile_words();
+}
+
+std::vector<u8> Engine::envelope_window(i64 r0, i64 c0, i64 rows, i64 cols) {
+    need_envelope("envelope_window()");
+    ViewEnvelope v(view_env_);
+    return window(r0, c0, rows, cols);
+}
+
+std::vector<u32> Engine::envelope_density(i64 block_rows, i64 block_cols) {
+    need_envelope("envelope_density()");
+    ViewEnvelope v(view_env_);
+    return density(block_rows, block_cols);
+}
+
+u64 Engine::envelope_population() {
+    need_envelope("envelope_population()");
+    ViewEnvelope v(view_env_);
+    return population();
+}
+
+void Engine::envelope_clear() {
+    need_envelope("envelope_clear()");
+    envelope_reset();
+}
+
+// ---------------------------------------------------------------------------------------------
 // Signatures (signature mode's record: census_host_ the populations, sig_host_ the signatures)
 // ---------------------------------------------------------------------------------------------
 
@@ -722,6 +800,7 @@ std::vector<u32> Engine::density(i64 block_rows, i64 block_cols) {
 void Engine::stamp(const RlePattern& p, i64 r0, i64 c0, StampMode mode) {
     check_stamp(p, r0, c0);
     stamp_local(p, r0, c0, mode);
+    if (cfg_.envelope) envelope_merge_local(false);  // E |= board: what the stamp removed stays in E
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -735,6 +814,7 @@ class CpuEngine : public Engine {
     CpuEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transport> t) : Engine(g, c, std::move(t)) {
         a_.assign((size_t)L_.words(), 0);
         b_.assign((size_t)L_.words(), 0);
+        if (cfg_.envelope) env_.assign((size_t)L_.words(), 0);
         cur_ = a_.data();
         oth_ = b_.data();
     }
@@ -743,17 +823,23 @@ class CpuEngine : public Engine {
 
     std::vector<u64> tile_words() override {
         std::vector<u64> d((size_t)(L_.h * L_.nw));
-        cpu::extract_words(cur_, L_, d.data());
+        cpu::extract_words(view_buf(), L_, d.data());
         return d;
     }
     void set_tile_words(const std::vector<u64>& dense) override {
         if ((i64)dense.size() != L_.h * L_.nw) throw Error("set_tile_words: wrong size");
         cpu::insert_words(cur_, L_, dense.data());
         refresh_local(cur_);
+        if (cfg_.envelope) envelope_reset();
     }
     std::pair<u64, u64> local_reduce() override {
-        return {cpu::population(cur_, L_),
-                cpu::fingerprint(cur_, L_, g_.row0, g_.word0(), g_.global_words())};
+        return {cpu::population(view_buf(), L_),
+                cpu::fingerprint(view_buf(), L_, g_.row0, g_.word0(), g_.global_words())};
+    }
+    // E = (reset ? 0 : E) | the tile's own cells (ghost rows and words of E stay 0)
+    void envelope_merge_local(bool reset) override {
+        if (reset) std::fill(env_.begin(), env_.end(), 0);
+        cpu::envelope_or(env_.data(), cur_, L_);
     }
     u64 local_signature() override { return cpu::signature(cur_, L_, g_.row0, g_.word0()); }
     void snapshot_local() override { snap_.assign(cur_, cur_ + L_.words()); }
@@ -770,7 +856,7 @@ class CpuEngine : public Engine {
         check_window(r0, c0, rows, cols);
         for (const Piece& p : pieces(g_, r0, c0, rows, cols))
             for (i64 r = 0; r < p.rows; ++r) {
-                const u64* row = cur_ + L_.index(p.tr + r, 0);
+                const u64* row = view_buf() + L_.index(p.tr + r, 0);
                 u8* o = out + (p.wr + r) * stride + p.wc;
                 for (i64 c = 0; c < p.cols; ++c) {
                     const i64 tc = p.tc + c;
@@ -783,7 +869,7 @@ class CpuEngine : public Engine {
         check_density(block_rows, block_cols);
         const i64 gcols = ceil_div(g_.dec.W, block_cols), wpb = block_cols / 64;
         for (i64 r = 0; r < L_.h; ++r) {
-            const u64* row = cur_ + L_.index(r, 0);
+            const u64* row = view_buf() + L_.index(r, 0);
             u32* line = counts + ((g_.row0 + r) / block_rows) * gcols;
             for (i64 c = 0; c < L_.nw; ++c)
                 line[(g_.word0() + c) / wpb] += (u32)__builtin_popcountll(row[c] & storage_mask(c, L_.w));
@@ -874,7 +960,8 @@ class CpuEngine : public Engine {
             density_host_.resize(density_host_.size() + add, 0);
             dens = cpu::DensityOut{&density_geo_, density_host_.data() + (density_host_.size() - add)};
         }
-        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, place, counts, sigs, film, dens);
+        u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, place, counts, sigs, film, dens,
+                                  cfg_.envelope ? env_.data() : nullptr);
         if (res != cur_) std::swap(cur_, oth_);
         if (self_x()) cpu::fill_ghost_cols_wrap(cur_, L_, 0, L_.h);
     }
@@ -895,7 +982,9 @@ class CpuEngine : public Engine {
     }
 
    private:
+    const u64* view_buf() const { return view_env_ ? env_.data() : cur_; }
     std::vector<u64> a_, b_, snap_;
+    std::vector<u64> env_;  // envelope mode: E in the board's layout
     u64* cur_;
     u64* oth_;
     std::vector<std::vector<u64>> stage_s_, stage_r_;

@@ -74,6 +74,9 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
                                   "at least %zu of them (GOL_DENSITY_FILM_MB; density() reads any grid)",
                                   (long long)density_geo_.grid_rows, (long long)density_geo_.grid_cols, slot_bytes(), mb, kFilmMinFrames));
     }
+    if (cfg_.envelope && cfg_.kernel_depth > hipk::max_envelope_depth(cfg_.rule.nbhd))
+        throw Error(strprintf("envelope: kernel_depth %d exceeds the envelope kernel's deepest pass, %d generations (GOL_KERNEL_DEPTH)",
+                              cfg_.kernel_depth, hipk::max_envelope_depth(cfg_.rule.nbhd)));
     if (rule_ && kernel_ == "auto") kernel_ = "rule";  // (any other name is refused below)
     hipk::ensure_trash();  // before any launch or graph capture
     // Kernel pass depth K (generations per HBM pass) vs halo depth R (generations per
@@ -116,6 +119,12 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
     const size_t bytes = (size_t)(L_.words() + hipk::kSlackRows * L_.pitch) * 8;
     for (int i = 0; i < 2; ++i) HIP_CHECK(hipMalloc(&buf_[i], bytes));
     alloc_bytes_ = bytes;
+    if (cfg_.envelope && hipMalloc(&d_env_, bytes) != hipSuccess) {  // one more board-sized buffer
+        (void)hipGetLastError();
+        d_env_ = nullptr;
+        for (int i = 0; i < 2; ++i) hipFree(buf_[i]);
+        throw Error(strprintf("envelope: no device memory for the envelope, a third board buffer of %zu bytes", bytes));
+    }
     device_transport_ = t_->device_buffers() && cfg_.transport != "host";
     // Register both boards (their ghost and edge rows are what the one-tile exchanges send and receive)
     // with the device transport: RCCL's user-buffer registration (ncclCommRegister) lets peer
@@ -150,6 +159,7 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
     // null-stream calls such as hipMemset, or a pageable hipMemcpy whose DMA may still be in
     // flight when it returns, would NOT be ordered before their kernels.)
     for (int i = 0; i < 2; ++i) HIP_CHECK(hipMemsetAsync(buf_[i], 0, bytes, s_comp_));
+    if (d_env_) HIP_CHECK(hipMemsetAsync(d_env_, 0, bytes, s_comp_));
     HIP_CHECK(hipStreamSynchronize(s_comp_));
     // Stream-ordering events (never read by the host for data; event_flags: no system-scope fence)
     HIP_CHECK(hipEventCreateWithFlags(&ev_ready_, event_flags()));
@@ -251,7 +261,7 @@ HipEngine::~HipEngine() {
     for (void* q : {(void*)res_status_, (void*)res_scratch_[0], (void*)res_scratch_[1]})
         if (q) hipFree(q);
     for (void* p : deferred_free_) hipFree(p);
-    for (void* p : {(void*)d_view_, (void*)d_grid_, (void*)d_pat_, (void*)d_census_, (void*)d_snap_})
+    for (void* p : {(void*)d_view_, (void*)d_grid_, (void*)d_pat_, (void*)d_census_, (void*)d_snap_, (void*)d_env_})
         if (p) hipFree(p);
     if (h_view_) hipHostFree(h_view_);
     hipFree(d_red_);
@@ -275,7 +285,7 @@ std::vector<u64> HipEngine::tile_words() {
     std::vector<u64> d((size_t)(L_.h * L_.nw));
     // stream-ordered (never the legacy null stream: in thread mode another rank's engine may be
     // capturing a graph, and a null-stream copy would have to depend on the capturing stream)
-    HIP_CHECK(hipMemcpy2DAsync(d.data(), (size_t)L_.nw * 8, buf_[cur_] + L_.index(0, 0), (size_t)L_.pitch * 8,
+    HIP_CHECK(hipMemcpy2DAsync(d.data(), (size_t)L_.nw * 8, view_buf() + L_.index(0, 0), (size_t)L_.pitch * 8,
                                (size_t)L_.nw * 8, (size_t)L_.h, hipMemcpyDeviceToHost, s_comp_));
     HIP_CHECK(hipStreamSynchronize(s_comp_));
     // device storage is split-format (bits.hpp); the API is natural-order words
@@ -304,6 +314,19 @@ void HipEngine::set_tile_words(const std::vector<u64>& dense) {
     post(buf_[cur_], s_comp_);
     mark_ready();
     synchronize();
+    if (cfg_.envelope) envelope_reset();
+}
+
+// Envelope mode's reset and stamp follow-up (aux_kernels.hip): the board is canonical and the streams are drained
+// where this is called (init, set_tile_words, stamp), and envelope_clear() makes them so.
+void HipEngine::envelope_merge_local(bool reset) {
+    sync_canonical();
+    synchronize();
+    check_res_status();
+    if (reset) HIP_CHECK(hipMemsetAsync(d_env_, 0, alloc_bytes_, s_comp_));  // (ghost rows and words of E stay 0)
+    hipk::launch_envelope_merge(d_env_, buf_[cur_], L_, reset, s_comp_);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
 }
 
 // Census mode: the call's counts go to device slots reserved here (census_begin), in chunks of at most
@@ -311,6 +334,17 @@ void HipEngine::set_tile_words(const std::vector<u64>& dense) {
 // Signature mode records the same way, in slots of its own size (slot_words()), film mode in slots of one frame and
 // density-film mode in slots of one map.
 void HipEngine::run(u64 generations) {
+    if (cfg_.envelope) {  // (no slots: every pass ORs into the one envelope; a timing sample into none)
+        env_at_ = census_mute_ ? nullptr : d_env_;
+        try {
+            run_counted(generations);
+        } catch (...) {
+            env_at_ = nullptr;
+            throw;
+        }
+        env_at_ = nullptr;
+        return;
+    }
     if (!recording() || census_mute_) return run_counted(generations);
     while (generations > 0) {
         const u64 n = std::min<u64>(generations, max_slots());
@@ -511,7 +545,7 @@ void HipEngine::finish_init() {
     if (!split_ && !dual_ && kern_[0] == "pipe")
         stats_.kernel = strprintf("pipe@%d(%dx%d,%d/CU)", pipe_k_, pipe_cur_.nw - 1, pipe_cur_.l, pipe_cur_.wg);
     if (rule_) {
-        const std::string rk = strprintf(cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", kdepth_);
+        const std::string rk = strprintf(cfg_.envelope ? "envelope@%d" : cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", kdepth_);
         stats_.kernel = split_ ? rk + "+boundary:" + rk : rk;
     }
     if (res_) {
@@ -538,7 +572,7 @@ void HipEngine::finish_init() {
                 const PassKernel pk = pass_kernel(kind, ps[j]);
                 c += (j ? "+" : "") + (pk == PK_PIPE   ? strprintf("pipe@%d(%dx%d,%d/CU)", ps[j], g->nw - 1, g->l, g->wg)
                                        : pk == PK_TILE ? strprintf("tile@%d", ps[j])
-                                       : pk == PK_RULE ? strprintf(cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", ps[j])
+                                       : pk == PK_RULE ? strprintf(cfg_.envelope ? "envelope@%d" : cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", ps[j])
                                                        : strprintf("temporal@%d", ps[j]));
             }
             tn += strprintf("%scut%d=%s", tn.empty() ? "" : " ", k, c.c_str());
@@ -804,7 +838,9 @@ void HipEngine::launch(int kind, int k, i64 e, const u64* src, u64* dst, hipStre
             pipe_used_ = true;
         } else if (pk == PK_RULE) {
             const hipk::BoardEdges edges{g_.row0, g_.dec.H, g_.word0(), g_.dec.W};
-            if (cfg_.density_film.on) {
+            if (cfg_.envelope) {
+                hipk::launch_step_envelope(k, cfg_.rule, edges, dead_edges(), L_.w, src, dst, env_at_, p.d, p.waves, sp, s);
+            } else if (cfg_.density_film.on) {
                 DensityGeo grid = density_geo_;  // (a block larger than the board counts what one of the board's size does)
                 grid.block_rows = std::min(grid.block_rows, g_.dec.H);
                 grid.block_words = std::min(grid.block_words, ceil_div(g_.dec.W, 64));

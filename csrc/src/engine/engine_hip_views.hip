@@ -46,7 +46,7 @@ void HipEngine::read_window_local(i64 r0, i64 c0, i64 rows, i64 cols, u8* out, i
     for (size_t i = 0; i < ps.size(); ++i) {
         const Piece& p = ps[i];
         const size_t n = (size_t)(p.rows * p.cols);
-        hipk::launch_window_bytes(buf_[cur_], L_, {p.tr, p.tc, p.rows, p.cols}, d_view_ + at[i], s_comp_);
+        hipk::launch_window_bytes(view_buf(), L_, {p.tr, p.tc, p.rows, p.cols}, d_view_ + at[i], s_comp_);
         HIP_CHECK(hipGetLastError());
         // only the piece's bytes cross to the host
         HIP_CHECK(hipMemcpyAsync(host + at[i], d_view_ + at[i], n, hipMemcpyDeviceToHost, s_comp_));
@@ -70,7 +70,7 @@ void HipEngine::density_local(i64 block_rows, i64 block_cols, u32* counts) {
     grow_device((void**)&d_grid_, &d_grid_cap_, bytes);
     u32* host = reinterpret_cast<u32*>(view_host(bytes));
     HIP_CHECK(hipMemsetAsync(d_grid_, 0, bytes, s_comp_));
-    hipk::launch_density(buf_[cur_], L_, g_.row0, g_.word0(), block_rows, block_cols / 64, gcols, d_grid_, s_comp_);
+    hipk::launch_density(view_buf(), L_, g_.row0, g_.word0(), block_rows, block_cols / 64, gcols, d_grid_, s_comp_);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(host, d_grid_, bytes, hipMemcpyDeviceToHost, s_comp_));  // only the grid leaves the device
     HIP_CHECK(hipStreamSynchronize(s_comp_));

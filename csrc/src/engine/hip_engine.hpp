@@ -122,7 +122,7 @@ class HipEngine : public Engine {
         sync_canonical();
         check_res_status();
         HIP_CHECK(hipMemsetAsync(d_red_, 0, 2 * sizeof(u64), s_comp_));
-        hipk::launch_reduce_board(buf_[cur_], L_, g_.row0, g_.word0(), g_.global_words(), d_red_, s_comp_);
+        hipk::launch_reduce_board(view_buf(), L_, g_.row0, g_.word0(), g_.global_words(), d_red_, s_comp_);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(h_red_, d_red_, 2 * sizeof(u64), hipMemcpyDeviceToHost, s_comp_));
         HIP_CHECK(hipStreamSynchronize(s_comp_));
@@ -311,6 +311,7 @@ class HipEngine : public Engine {
     // The streaming kernel of this engine: step_rule under a rule (rule_), else step_temporal.
     // (in census mode step_census, at its own depths, on either boundary)
     bool depth_ok(int k) const {
+        if (cfg_.envelope) return k >= 1 && k <= hipk::max_envelope_depth(cfg_.rule.nbhd);
         if (cfg_.density_film.on) return k >= 1 && k <= hipk::max_density_depth(cfg_.rule.nbhd);
         if (cfg_.film.on) return k >= 1 && k <= hipk::max_film_depth(cfg_.rule.nbhd);
         if (cfg_.signature) return k >= 1 && k <= hipk::max_signature_depth(cfg_.rule.nbhd);
@@ -318,6 +319,7 @@ class HipEngine : public Engine {
         return rule_ ? hipk::rule_depth_supported(k, cfg_.rule.nbhd) : hipk::step_depth_supported(k);
     }
     int max_depth() const {
+        if (cfg_.envelope) return hipk::max_envelope_depth(cfg_.rule.nbhd);
         if (cfg_.density_film.on) return hipk::max_density_depth(cfg_.rule.nbhd);
         if (cfg_.film.on) return hipk::max_film_depth(cfg_.rule.nbhd);
         if (cfg_.signature) return hipk::max_signature_depth(cfg_.rule.nbhd);
@@ -325,6 +327,7 @@ class HipEngine : public Engine {
         return rule_ ? hipk::max_rule_depth(cfg_.rule.nbhd) : hipk::max_step_depth();
     }
     int blocks_per_cu(int k, u32 flags) const {
+        if (cfg_.envelope) return hipk::envelope_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
         if (cfg_.density_film.on) return hipk::density_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
         if (cfg_.film.on) return hipk::film_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
         if (cfg_.signature) return hipk::signature_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
@@ -773,6 +776,14 @@ class HipEngine : public Engine {
     }
     static constexpr size_t kFilmMinFrames = 8;  // a window whose frames do not fit this often is refused at init
     size_t film_cap_ = 0;                        // frames (density-film mode: maps) the device buffer holds
+    // ----- envelope (EngineConfig::envelope) -----
+    // d_env_: E in the board's layout and size (alloc_bytes_), allocated with the boards.  env_at_: d_env_ inside a
+    // run() that is no timing sample, else null: every other launch (the init-time autotune, schedule timing, the
+    // hinted run's prediction) hands step_envelope a null envelope and leaves E untouched.
+    void envelope_merge_local(bool reset) override;
+    const u64* view_buf() const { return view_env_ ? d_env_ : buf_[cur_]; }  // what the readers read
+    u64* d_env_ = nullptr;
+    u64* env_at_ = nullptr;
     u64* d_snap_ = nullptr;  // snapshot(): a third board buffer (alloc_bytes_), allocated on first use
     bool res_ = false;  // supersteps run the resident kernel
     int res_kin_ = 0;   // its generations per in-kernel halo exchange

@@ -109,6 +109,19 @@ __global__ void k_naive_byte_step(const u8* __restrict__ src, u8* __restrict__ d
     }
 }
 
+// Envelope mode's reset and stamp follow-up: env = (reset ? 0 : env) | the tile's own cells of board (both in one
+// layout; the ghost rows and words of env stay 0).
+__global__ void k_envelope_merge(u64* __restrict__ env, const u64* __restrict__ board, i64 pitch, int R, i64 h, i64 nw, i64 w,
+                                 int reset) {
+    const i64 n = h * nw;
+    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (i64)gridDim.x * blockDim.x) {
+        const i64 r = e / nw, c = e - r * nw;
+        const i64 at = (r + R) * pitch + c + 1;
+        const u64 v = board[at] & storage_mask(c, w);
+        env[at] = reset ? v : (env[at] | v);
+    }
+}
+
 unsigned grid_for(i64 n, int block = 256, i64 cap = 256 * 16) {
     i64 g = ceil_div(n, block);
     if (g < 1) g = 1;
@@ -148,6 +161,11 @@ void launch_reduce_board(const u64* buf, const Layout& L, i64 grow0, i64 gword0,
                          hipStream_t s) {
     hipLaunchKernelGGL(k_reduce_board, dim3(grid_for(L.h * L.nw, 256, 2048)), dim3(256), 0, s, buf, L.pitch, L.R, L.h,
                        L.nw, L.w, grow0, gword0, gwords, (unsigned long long*)out);
+}
+
+void launch_envelope_merge(u64* env, const u64* board, const Layout& L, bool reset, hipStream_t s) {
+    hipLaunchKernelGGL(k_envelope_merge, dim3(grid_for(L.h * L.nw)), dim3(256), 0, s, env, board, L.pitch, L.R, L.h, L.nw, L.w,
+                       reset ? 1 : 0);
 }
 
 void launch_naive_byte_step(const u8* src, u8* dst, i64 w, i64 h, const u8* above, const u8* below, int threads,

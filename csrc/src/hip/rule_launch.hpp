@@ -20,6 +20,7 @@ const void* nbhd_census_kernel(Nbhd nbhd, int k, u32 flags, bool bounded);
 const void* nbhd_signature_kernel(Nbhd nbhd, int k, u32 flags, bool bounded);
 const void* nbhd_film_kernel(Nbhd nbhd, int k, u32 flags, bool bounded);  // (step_film: nbhd_film_kernel.hip)
 const void* nbhd_density_kernel(Nbhd nbhd, int k, u32 flags, bool bounded);  // (step_density: nbhd_density_kernel.hip)
+const void* nbhd_envelope_kernel(Nbhd nbhd, int k, u32 flags, bool bounded);  // (step_envelope: nbhd_envelope_kernel.hip)
 
 namespace {
 

@@ -1,7 +1,8 @@
-// gol-mi355x: the policies of step_rule_bounded, step_census, step_signature, step_film and step_density
-// (rule_runner.hpp tells what a policy is), in a header because each has two kernels: the Moore one in
-// rule_bounded_kernel.hip, census_kernel.hip, signature_kernel.hip, film_kernel.hip and density_kernel.hip, whose
-// headers explain the policies, and the von Neumann / hexagonal one in the nbhd_*.hip unit of the same family.
+// gol-mi355x: the policies of step_rule_bounded, step_census, step_signature, step_film, step_density and
+// step_envelope (rule_runner.hpp tells what a policy is), in a header because each has two kernels: the Moore one in
+// rule_bounded_kernel.hip, census_kernel.hip, signature_kernel.hip, film_kernel.hip, density_kernel.hip and
+// envelope_kernel.hip, whose headers explain the policies, and the von Neumann / hexagonal one in the nbhd_*.hip unit
+// of the same family.
 #pragma once
 
 #include "gol/signature.hpp"
@@ -347,6 +348,77 @@ struct DensityPolicy {
         }
 #pragma unroll
         for (int l = 0; l < K; ++l) flush(ty, l, brow);
+    }
+};
+
+// step_envelope's kernel argument: the envelope buffer, in the board's own layout (nullptr: touch nothing).
+struct EnvelopeArgs {
+    u64* env;
+};
+
+// The Tally of the envelope policy: the OR chains of the rows in flight.  nxt[l] is what level l - 1 made of its row
+// in this row iteration, cur[l] what it made one iteration earlier: the OR of generations 1 .. l of the row level l
+// outputs now.  Level 0 moves nxt to cur at the start of every iteration (renaming in the unrolled loop): cur[l] dies
+// at level l and nxt[l] is born at level l - 1, so 2 (K - 1) values live across the iterations, and two more inside.
+template <int K>
+struct EnvelopeTally {
+    u32 cur_lo[K], cur_hi[K], nxt_lo[K], nxt_hi[K];
+    __device__ __forceinline__ EnvelopeTally() {
+#pragma unroll
+        for (int l = 0; l < K; ++l) cur_lo[l] = cur_hi[l] = nxt_lo[l] = nxt_hi[l] = 0;
+    }
+};
+
+// step_envelope: the OR of a row's K outputs travels with the row through the levels; the last level ORs the owned
+// cells of it into the envelope word that lies where the runner stores the row (envelope_kernel.hip).
+template <int K, int MASK, bool BOUNDED>
+struct EnvelopePolicy {
+    static constexpr int kRowBarriers = 2;
+    EdgeMask<MASK> em;  // BOUNDED
+    OwnMask<MASK> own;
+    unsigned long long* ep;  // the envelope word of the row level K - 1 outputs next (dereferenced by owning lanes only)
+    const i64 pitch;
+    const bool on;  // (uniform)
+    using Tally = EnvelopeTally<K>;
+
+    __device__ __forceinline__ EnvelopePolicy(const LaneDesc& d, int nrows, const StepParams& p, const TileArgs& ta,
+                                              const EnvelopeArgs& ea)
+        : pitch(p.pitch), on(ea.env != nullptr) {
+        const bool stores = d.flags & LANE_STORE;  // (ahead of the masks: the prologue's order, PERFORMANCE.md section 23)
+        if (BOUNDED) em.template init<K>(d, ta);
+        own.template init<K>(stores, d, nrows, p, ta);
+        // level K - 1 first outputs in row iteration 2K, row counter K: tile row row0, the runner's first store
+        ep = reinterpret_cast<unsigned long long*>(ea.env) + ((i64)(d.row0 + p.R) * p.pitch + (d.col + 1));
+    }
+
+    // (BOUNDED) the loaded row: ghost rows and words hold the torus neighbour's cells
+    __device__ __forceinline__ void input(u32& lo, u32& hi, int i) const {
+        if (BOUNDED) em.apply(lo, hi, i);
+    }
+    // The (masked) output of level l joins the chain of its row; the last level's chain goes to the envelope.
+    __device__ __forceinline__ void level(Tally& ty, int l, u32& lo, u32& hi, int t) {
+        if (BOUNDED) em.apply(lo, hi, t);
+        if (l == 0) {
+#pragma unroll
+            for (int m = 1; m < K; ++m) {
+                ty.cur_lo[m] = ty.nxt_lo[m];
+                ty.cur_hi[m] = ty.nxt_hi[m];
+            }
+        }
+        const u32 e_lo = l == 0 ? lo : (ty.cur_lo[l] | lo), e_hi = l == 0 ? hi : (ty.cur_hi[l] | hi);
+        if (l + 1 < K) {
+            ty.nxt_lo[l + 1] = e_lo;
+            ty.nxt_hi[l + 1] = e_hi;
+            return;
+        }
+        if (!on) return;  // (uniform)
+        const u32 r = own.row(t);
+        const u32 m_lo = b3<kLutAnd3>(e_lo, own.own_lo, r), m_hi = b3<kLutAnd3>(e_hi, own.own_hi, r);
+        // (a lane with nothing to add sends nothing: dead regions cost no envelope traffic)
+        if ((m_lo | m_hi) != 0)
+            (void)__hip_atomic_fetch_or(ep, ((unsigned long long)m_hi << 32) | (unsigned long long)m_lo, __ATOMIC_RELAXED,
+                                        __HIP_MEMORY_SCOPE_AGENT);
+        ep += pitch;
     }
 };
 

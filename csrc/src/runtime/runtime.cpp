@@ -173,6 +173,7 @@ EngineConfig engine_config(const Options& o, const std::string& backend, int dev
     c.signature = o.signature;
     if (!o.film.empty()) c.film = parse_film(o.film);
     if (!o.density_film.empty()) c.density_film = parse_density_film(o.density_film);
+    c.envelope = o.envelope;
     c.tile_waves = (int)env_int("GOL_TILE_WAVES", 8);
     c.tune_tile_waves = getenv("GOL_TILE_WAVES") == nullptr;
     c.transport = (o.transport == "rccl" || o.transport == "p2p") ? "device" : o.transport;
@@ -462,6 +463,10 @@ void write_metrics(const Options& o, Engine& eng, const CliArgs& a, double durat
         f << "  \"density_film\": [" << s.density_film.rows << ", " << s.density_film.cols << "],\n";
     else
         f << "  \"density_film\": null,\n";
+    if (s.envelope)
+        f << "  \"envelope\": " << s.envelope_start << ",\n";
+    else
+        f << "  \"envelope\": null,\n";
     f << "  \"schedule\": \"" << s.schedule << "\",\n";
     f << "  \"autotune\": \"" << s.tuning << "\",\n";
     f << "  \"plan_waves\": " << s.plan_waves << ",\n  \"lane_efficiency\": " << s.lane_efficiency << ",\n";
@@ -544,6 +549,7 @@ int run_soups(const CliArgs& a, const Options& o, const LaunchInfo& li) {
     if (o.signature) throw Error("GOL_SOUPS with signature mode (GOL_SIGNATURE / GOL_SIGNATURE_OUT): a soup batch compares boards");
     if (!o.film.empty()) throw Error("GOL_SOUPS with film mode (GOL_FILM): a soup batch films nothing");
     if (!o.density_film.empty()) throw Error("GOL_SOUPS with density-film mode (GOL_DENSITY_FILM): a soup batch films nothing");
+    if (o.envelope) throw Error("GOL_SOUPS with envelope mode (GOL_ENVELOPE / GOL_ENVELOPE_OUT): a soup batch keeps no envelope");
     SoupConfig c;
     c.n = n;
     c.size = (i64)a.world_size;
@@ -607,6 +613,10 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
         if (!o.rle_out.empty() && dec.H * dec.W > kRleOutMaxCells)
             throw Error(strprintf("GOL_RLE_OUT: the %lld x %lld board has more than 2^26 cells, too large to gather on rank 0 "
                                   "and write as RLE (a checkpoint, GOL_CHECKPOINT_EVERY, holds any board)",
+                                  (long long)dec.H, (long long)dec.W));
+        if (!o.envelope_out.empty() && dec.H * dec.W > kRleOutMaxCells)
+            throw Error(strprintf("GOL_ENVELOPE_OUT: the %lld x %lld board has more than 2^26 cells, too large to gather on rank 0 "
+                                  "and write as RLE (read parts of the envelope with envelope_window())",
                                   (long long)dec.H, (long long)dec.W));
         constexpr u64 kFilmOutMaxBytes = (u64)1 << 30;
         if (!o.film_out.empty()) {
@@ -730,7 +740,8 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
             t->broadcast(&ok, sizeof(ok), 0);
             if (!ok) throw Error("GOL_DENSITY_FILM_OUT: cannot write " + o.density_film_out);
         }
-        if (!o.rle_out.empty()) {
+        // rank 0: the cells of the whole board as an RLE file with the run's rule (GOL_RLE_OUT, GOL_ENVELOPE_OUT)
+        auto write_board_rle = [&](const std::string& path, const std::vector<u8>& cells) {
             RlePattern out;
             out.rows = dec.H;
             out.cols = dec.W;
@@ -740,14 +751,29 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
                 out.bound_cols = dec.W;
                 out.bound_rows = dec.H;
             }
-            const std::vector<u8> cells = eng->window(0, 0, dec.H, dec.W);  // collective
+            out.words.assign((size_t)(out.rows * out.nw()), 0);
+            for (i64 r = 0; r < out.rows; ++r)
+                for (i64 c = 0; c < out.cols; ++c)
+                    if (cells[(size_t)(r * out.cols + c)]) out.set(r, c);
+            write_rle_file(path, out);
+        };
+        if (!o.envelope_out.empty()) {
+            // the run's envelope (collective); rank 0 writes it, and every rank learns whether that worked
+            const std::vector<u8> cells = eng->envelope_window(0, 0, dec.H, dec.W);
+            u64 ok = 1;
             if (rank == 0) {
-                out.words.assign((size_t)(out.rows * out.nw()), 0);
-                for (i64 r = 0; r < out.rows; ++r)
-                    for (i64 c = 0; c < out.cols; ++c)
-                        if (cells[(size_t)(r * out.cols + c)]) out.set(r, c);
-                write_rle_file(o.rle_out, out);
+                try {
+                    write_board_rle(o.envelope_out, cells);
+                } catch (const Error&) {
+                    ok = 0;
+                }
             }
+            t->broadcast(&ok, sizeof(ok), 0);
+            if (!ok) throw Error("GOL_ENVELOPE_OUT: cannot write " + o.envelope_out);
+        }
+        if (!o.rle_out.empty()) {
+            const std::vector<u8> cells = eng->window(0, 0, dec.H, dec.W);  // collective
+            if (rank == 0) write_board_rle(o.rle_out, cells);
         }
         t->barrier();
         return 0;

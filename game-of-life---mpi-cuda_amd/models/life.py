@@ -93,6 +93,14 @@ class Simulation:
                   included; passes of at most ``max_density_depth`` generations, eager launches; the maps wait in a device
                   buffer of GOL_DENSITY_FILM_MB MiB, default 64); without ``census``, ``signature``, ``film``, ``compat``,
                   ``subtiles=2`` or the specialised kernels.
+    envelope:     envelope mode (default off; GOL_ENVELOPE): the simulation keeps the OR of every generation of the board
+                  since the last reset, one bit per cell: every cell that was ever alive.  :meth:`init`, :meth:`set_board`,
+                  :meth:`restore` and :meth:`envelope_clear` reset it to the current board; :meth:`stamp` ORs the stamped
+                  board in.  Read with :meth:`envelope`, :meth:`envelope_window`, :meth:`envelope_density` and
+                  :meth:`envelope_population`.  HIP: a third board-sized buffer, and the envelope kernel ``step_envelope``
+                  ORs into it inside every pass, for every rule, neighbourhood and either boundary (generic-kernel speed,
+                  B3/S23 included; passes of at most ``max_envelope_depth`` generations, eager launches); without
+                  ``census``, ``signature``, ``film``, ``density_film``, ``compat``, ``subtiles=2`` or the specialised kernels.
     compat:       reproduce the reference's halo quirks (frozen gen-0 halos, P<=2 swap).
     watchdog:     seconds without progress before the job is aborted (0 = off; GOL_WATCHDOG).
     """
@@ -132,6 +140,7 @@ class Simulation:
         signature: Optional[bool] = None,
         film=None,
         density_film=None,
+        envelope: Optional[bool] = None,
     ):
         self.transport = transport if transport is not None else _gol.SelfTransport()
         P, rank = self.transport.size(), self.transport.rank()
@@ -280,6 +289,25 @@ class Simulation:
                     "per generation; read finer grids with density()"
                 )
             cfg.density_film = density_film
+        if envelope is None:  # (read per call, as the census mode is)
+            envelope = os.environ.get("GOL_ENVELOPE", "0") not in ("", "0")
+        if envelope:
+            if cfg.census or cfg.signature or cfg.film is not None or cfg.density_film is not None:
+                raise ValueError(
+                    "envelope with census=True, signature=True, film or density_film: one in-kernel record per simulation"
+                )
+            if compat:
+                raise ValueError("envelope with compat=True: compat mode runs the reference's loop, not the envelope kernel")
+            if int(subtiles) == 2:
+                raise ValueError("envelope with subtiles=2: the sub-tile halves do not run the envelope kernel")
+            if self.backend == "hip" and kernel in ("temporal", "tile", "pipe", "resident", "lds"):
+                raise ValueError(f"kernel {kernel!r} keeps no envelope: the envelope kernel runs every pass (use auto or rule)")
+            if self.backend == "hip" and int(kernel_depth) > _gol.max_envelope_depth():
+                raise ValueError(
+                    f"envelope: kernel_depth {kernel_depth} exceeds the envelope kernel's deepest pass, "
+                    f"{_gol.max_envelope_depth()} generations"
+                )
+        cfg.envelope = bool(envelope)
         cfg.subtiles = int(subtiles)  # 2 / 0 / -1 auto: two sub-tiles per rank on two streams (HIP, 1-D)
         cfg.run_hint = int(run_hint)  # generations of the runs to come: one replay graph covers them
         cfg.rows_per_wave = rows_per_wave
@@ -424,6 +452,43 @@ class Simulation:
                 "density_film_clear() needs a simulation built with density_film=(block_rows, block_cols) (or GOL_DENSITY_FILM)"
             )
         self.engine.density_film_clear()
+
+    def _need_envelope(self, what: str) -> None:
+        if not self.config.envelope:
+            raise ValueError(f"{what} needs a simulation in envelope mode, built with envelope=True (or GOL_ENVELOPE=1)")
+
+    def envelope(self):
+        """``(start, cells)``: ``cells`` is this rank's tile of the envelope as :meth:`board` returns the board, a
+        ``(h, w)`` uint8 array with a 1 for every cell that was alive in any of the generations ``start ..
+        generation``; ``start`` is the generation of the last reset (:meth:`init`, :meth:`load_rle`, :meth:`set_board`,
+        :meth:`restore`, :meth:`envelope_clear`).  :func:`ops.numpy_envelope` is its oracle.  Needs ``envelope=True``."""
+        self._need_envelope("envelope()")
+        start, words = self.engine.envelope()
+        return int(start), unpack_words(words, self.geometry.w)
+
+    def envelope_window(self, r0: int, c0: int, rows: int, cols: int) -> np.ndarray:
+        """:meth:`window` of the envelope: same coordinates, wrapping and bounded-board checks.  Collective."""
+        self._need_envelope("envelope_window()")
+        self._check_inside("envelope_window", int(r0), int(c0), int(rows), int(cols))
+        return self.engine.envelope_window(int(r0), int(c0), int(rows), int(cols))
+
+    def envelope_density(self, block_rows: int, block_cols: Optional[int] = None) -> np.ndarray:
+        """:meth:`density` of the envelope: ever-alive cells per block of the global board.  Collective."""
+        self._need_envelope("envelope_density()")
+        block_cols = block_rows if block_cols is None else block_cols
+        if int(block_rows) < 1 or int(block_cols) < 64 or int(block_cols) % 64:
+            raise ValueError(f"density blocks are >= 1 rows x a multiple of 64 columns, got {block_rows} x {block_cols}")
+        return self.engine.envelope_density(int(block_rows), int(block_cols))
+
+    def envelope_population(self) -> int:
+        """The number of cells of the global board that were ever alive since the last reset (collective)."""
+        self._need_envelope("envelope_population()")
+        return int(self.engine.envelope_population())
+
+    def envelope_clear(self) -> None:
+        """Reset the envelope to the current board; it starts again at the generation reached."""
+        self._need_envelope("envelope_clear()")
+        self.engine.envelope_clear()
 
     def snapshot(self) -> None:
         """Keep a copy of the current board (a third board buffer, allocated on first use) for :meth:`snapshot_diff`."""

@@ -5,6 +5,7 @@ from .oracle import (  # noqa: F401
     initial_board,
     numpy_census,
     numpy_density_film,
+    numpy_envelope,
     numpy_film,
     numpy_signature,
     numpy_signatures,

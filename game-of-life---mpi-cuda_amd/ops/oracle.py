@@ -293,6 +293,20 @@ def numpy_soup_settle(board: np.ndarray, rule, max_gens: int, transient: bool = 
     return period, tr, g, int(b.sum(dtype=np.uint64)), b
 
 
+def numpy_envelope(board: np.ndarray, rule, gens: int, bounded: bool = False, return_board: bool = False):
+    """The envelope of ``board`` over generations ``0 .. gens`` under ``rule`` as a uint8 array of the board's shape (the
+    oracle of the engines' envelope mode): a 1 for every cell alive in the board itself or after any of the ``gens``
+    generations, on the torus or, ``bounded``, on a board with dead edges.  One generation of :func:`numpy_step_rule` /
+    :func:`numpy_step_rule_bounded` at a time, ORed here.  ``return_board`` also returns the last board."""
+    step = numpy_step_rule_bounded if bounded else numpy_step_rule
+    b = np.asarray(board, dtype=np.uint8)
+    env = (b != 0).astype(np.uint8)
+    for _ in range(int(gens)):
+        b = step(b, rule, 1)
+        env |= b
+    return (env, b) if return_board else env
+
+
 def torch_step_rule(board, rule, generations: int = 1, device=None):
     """A life-like rule on a torus with torch conv2d (fp32, exact for counts <= 8).  Returns a torch uint8 tensor."""
     import torch
