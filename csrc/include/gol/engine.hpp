@@ -23,6 +23,7 @@
 #include <utility>
 #include <vector>
 
+#include "gol/cells.hpp"
 #include "gol/density_film.hpp"
 #include "gol/film.hpp"
 #include "gol/geometry.hpp"
@@ -287,6 +288,28 @@ class Engine {
     void check_density(i64 block_rows, i64 block_cols) const;
     void check_stamp(const RlePattern& p) const;
     void check_stamp(const RlePattern& p, i64 r0, i64 c0) const;
+    // ----- dense cells: the tensor readers and writers (gol/cells.hpp) -----
+    // The caller's buffer is one element per cell (u8, f16, bf16 or f32; exact 0 and 1 out, != 0 alive in).  HIP
+    // backend: device memory of the engine's device, verified with hipPointerGetAttributes before anything is launched,
+    // and the conversion is a kernel (src/hip/tensor_kernels.hip); CPU backend: host memory and a host loop.  Every call
+    // checks numel against the cells it moves, enqueues on the engine's compute stream and synchronises it before
+    // returning.  The tile and envelope calls act on this rank's own tile on any rank count; the window and film calls
+    // are for one rank and throw, naming the rank count, on more (summing the ranks' parts on the device is not built).
+    void read_tile_cells(const CellBuffer& dst);      // h x w cells of this rank's tile
+    void read_envelope_cells(const CellBuffer& dst);  // this rank's tile of the envelope (envelope mode)
+    // set_tile_words() from dense cells, with everything it does afterwards: ghost refresh, envelope reset; the
+    // per-generation records run on.
+    void write_tile_cells(const CellBuffer& src);
+    // window()'s rectangle and checks; the seams are crossed by addressing (the rectangle's at most four pieces in one launch)
+    void read_window_cells(i64 r0, i64 c0, i64 rows, i64 cols, const CellBuffer& dst);
+    // Film mode: `generations` generations, their frames (generations x rows x cols cells) unpacked on the way into dst
+    // instead of recorded: run() in chunks of film_chunk() generations, each chunk's packed frames converted at its
+    // frame offset and dropped.  Needs an empty film record (throws, saying to call film_clear() first); ends as
+    // film_clear() does, with an empty record that starts at the generation reached.
+    void run_film_cells(u64 generations, const CellBuffer& dst);
+    CellSource tile_source(const u64* buf, i64 r0, i64 c0, i64 rows, i64 cols) const;  // a rectangle of a buffer in layout L_
+    CellSource film_source(const u64* frames, i64 words, i64 n) const;                // n packed frames (gol/film.hpp)
+
     // Collective: align the ranks right before a timed region.  Host barrier; with a device
     // transport also a 1-element all-reduce on the compute stream, waited for, so every rank leaves
     // when the collective has completed on the GPUs, not when a host barrier happened to release it.
@@ -409,6 +432,17 @@ class Engine {
     void need_envelope(const char* what) const;
     bool view_env_ = false;
     u64 env_start_ = 0;
+    // Dense cells: the backends' parts.  check_cell_pointer: throw unless the buffer's memory is the backend's kind
+    // (HIP: device memory of the engine's device; CPU: nothing to ask).  read_rect_cells: the rectangle of the board
+    // (view_env_: the envelope) in tile coordinates, wrapping at the tile's edges.  write_tile_cells_local: the cells
+    // into the tile, then what set_tile_words() does after its copy.  film_chunk: the generations run_film_cells() runs
+    // between two drains; film_drain_cells: the `frames` frames run() has just recorded, converted into dst from frame
+    // `at` on, and the record empty again.
+    virtual void check_cell_pointer(const CellBuffer& b, const char* what) = 0;
+    virtual void read_rect_cells(i64 r0, i64 c0, i64 rows, i64 cols, const CellBuffer& dst) = 0;
+    virtual void write_tile_cells_local(const CellBuffer& src) = 0;
+    virtual size_t film_chunk() const = 0;
+    virtual void film_drain_cells(size_t frames, const CellBuffer& dst, size_t at) = 0;
 
     Geometry g_;
     EngineConfig cfg_;

@@ -24,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "gol/cells.hpp"
 #include "gol/common.hpp"
 #include "gol/rule.hpp"
 
@@ -101,6 +102,13 @@ class SoupBatch {
     std::vector<SoupRecord> records();
     // The boards of the soups idx (0 <= idx < n), one byte per cell, (k, S, S).
     std::vector<u8> boards(const std::vector<i64>& idx);
+    // Dense cells (gol/cells.hpp; HIP: device memory of the batch's device, verified before anything is launched, and a
+    // kernel of src/hip/tensor_kernels.hip; CPU: host memory, a host loop).  Both check numel, run on the batch's stream
+    // and synchronise it before returning.
+    // The boards of the soups first .. first + count - 1 as (count, S, S) elements, exact 0 and 1.
+    void read_boards_cells(i64 first, i64 count, const CellBuffer& dst);
+    // init_words() from (n, S, S) elements, alive iff != 0.
+    void init_cells(const CellBuffer& src);
     SoupStats stats() const;
     // Waits for the launches of step() (HIP; every other call returns finished work).
     virtual void synchronize() {}
@@ -117,6 +125,11 @@ class SoupBatch {
     virtual u64 do_transient(u32 gens) = 0;                   // one launch; returns the settled soups still without
     virtual void do_fetch_states(SoupState* out) = 0;
     virtual void do_fetch_board(i64 soup, u64* split) = 0;
+    virtual void do_read_cells(i64 first, i64 count, const CellBuffer& dst) = 0;
+    virtual void do_init_cells(const CellBuffer& src) = 0;  // the boards and, as do_upload, the states
+    // the soups first .. first + count - 1 of a store of n x S x m words
+    CellSource soup_source(const u64* store, i64 first, i64 count) const;
+    CellTarget soup_target(u64* store) const;
 
     SoupConfig cfg_;
     bool searching_ = false;

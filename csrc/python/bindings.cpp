@@ -93,6 +93,18 @@ py::array_t<u64> words_to_numpy(const std::vector<u64>& w, i64 rows, i64 nw) {
     return a;
 }
 
+// A dense-cell call on (data_ptr, type code, numel), without the GIL; a gol::Error becomes a ValueError.
+template <typename F>
+void cells_call(F f, uintptr_t ptr, int code, i64 numel) {
+    try {
+        const CellBuffer b{reinterpret_cast<void*>(ptr), cell_type_from_code(code), numel};
+        py::gil_scoped_release r;
+        f(b);
+    } catch (const Error& e) {
+        throw py::value_error(e.what());
+    }
+}
+
 py::dict stats_dict(const EngineStats& s) {
     py::dict d;
     d["generations"] = s.generations;
@@ -546,6 +558,28 @@ PYBIND11_MODULE(_gol, m) {
                 e.stamp(p, r0, c0, m);
             },
             py::arg("pattern"), py::arg("r0"), py::arg("c0"), py::arg("mode") = "or")
+        // dense cells (gol/cells.hpp): (data_ptr, element type code 0 u8 / 1 f16 / 2 bf16 / 3 f32, numel) of a caller's
+        // buffer, device memory on the HIP backend and host memory on the CPU backend; what a call refuses is a ValueError
+        .def("read_tile_cells", [](Engine& e, uintptr_t ptr, int code, i64 numel) {
+            cells_call([&](const CellBuffer& b) { e.read_tile_cells(b); }, ptr, code, numel);
+        })
+        .def("read_envelope_cells", [](Engine& e, uintptr_t ptr, int code, i64 numel) {
+            u64 start = 0;
+            cells_call([&](const CellBuffer& b) {
+                start = e.envelope_start();
+                e.read_envelope_cells(b);
+            }, ptr, code, numel);
+            return start;
+        })
+        .def("write_tile_cells", [](Engine& e, uintptr_t ptr, int code, i64 numel) {
+            cells_call([&](const CellBuffer& b) { e.write_tile_cells(b); }, ptr, code, numel);
+        })
+        .def("read_window_cells", [](Engine& e, i64 r0, i64 c0, i64 rows, i64 cols, uintptr_t ptr, int code, i64 numel) {
+            cells_call([&](const CellBuffer& b) { e.read_window_cells(r0, c0, rows, cols, b); }, ptr, code, numel);
+        })
+        .def("run_film_cells", [](Engine& e, u64 generations, uintptr_t ptr, int code, i64 numel) {
+            cells_call([&](const CellBuffer& b) { e.run_film_cells(generations, b); }, ptr, code, numel);
+        })
         .def("device_barrier", &Engine::device_barrier, py::call_guard<py::gil_scoped_release>())
         .def("phase_probe", &Engine::phase_probe, py::arg("k"), py::call_guard<py::gil_scoped_release>())
         .def("time_runs", &Engine::time_runs, py::arg("gens"), py::arg("reps"), py::call_guard<py::gil_scoped_release>())
@@ -753,6 +787,13 @@ PYBIND11_MODULE(_gol, m) {
                  std::memcpy(a.mutable_data(), cells.data(), cells.size());
                  return a;
              })
+        // dense cells, as the Engine's: (data_ptr, element type code, numel)
+        .def("read_boards_cells", [](SoupBatch& b, i64 first, i64 count, uintptr_t ptr, int code, i64 numel) {
+            cells_call([&](const CellBuffer& c) { b.read_boards_cells(first, count, c); }, ptr, code, numel);
+        })
+        .def("init_cells", [](SoupBatch& b, uintptr_t ptr, int code, i64 numel) {
+            cells_call([&](const CellBuffer& c) { b.init_cells(c); }, ptr, code, numel);
+        })
         .def("synchronize",
              [](SoupBatch& b) {
                  py::gil_scoped_release r;

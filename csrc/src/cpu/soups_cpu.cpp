@@ -123,6 +123,45 @@ std::vector<u8> SoupBatch::boards(const std::vector<i64>& idx) {
     return out;
 }
 
+CellSource SoupBatch::soup_source(const u64* store, i64 first, i64 count) const {
+    const i64 S = cfg_.size, M = m(), wps = words_per_soup();
+    CellSource s;
+    s.base = store + first * wps;
+    s.words = count * wps;
+    s.frame_stride = wps, s.row_stride = M;
+    s.n = count, s.rows = S, s.cols = S;
+    s.r0 = 0, s.H = S, s.c0 = 0, s.W = S;
+    s.w0 = 0, s.gwords = M, s.fw = M;
+    return s;
+}
+
+CellTarget SoupBatch::soup_target(u64* store) const {
+    CellTarget t;
+    t.base = store;
+    t.words = cfg_.n * words_per_soup();
+    t.row_stride = m(), t.rows = cfg_.n * cfg_.size, t.cols = cfg_.size;
+    return t;
+}
+
+void SoupBatch::read_boards_cells(i64 first, i64 count, const CellBuffer& dst) {
+    if (first < 0 || count < 1 || first > cfg_.n - count)
+        throw Error(strprintf("soups: read_boards_cells(): soups %lld .. %lld are outside 0 .. %lld", (long long)first,
+                              (long long)(first + count - 1), (long long)cfg_.n - 1));
+    if (dst.numel != count * cfg_.size * cfg_.size)
+        throw Error(strprintf("soups: read_boards_cells(): the buffer holds %lld elements, the cells are %lld", (long long)dst.numel,
+                              (long long)(count * cfg_.size * cfg_.size)));
+    do_read_cells(first, count, dst);
+}
+
+void SoupBatch::init_cells(const CellBuffer& src) {
+    if (src.numel != cfg_.n * cfg_.size * cfg_.size)
+        throw Error(strprintf("soups: init_cells(): the buffer holds %lld elements, the cells are %lld", (long long)src.numel,
+                              (long long)(cfg_.n * cfg_.size * cfg_.size)));
+    do_init_cells(src);
+    searching_ = false;
+    reached_ = launches_ = settled_ = 0;
+}
+
 SoupStats SoupBatch::stats() const {
     SoupStats s;
     s.kernel = strprintf("soups@%lld", (long long)cfg_.size) + (cfg_.rule.is_conway() ? "" : ":rule");
@@ -311,6 +350,13 @@ class CpuSoups final : public SoupBatch {
     void do_fetch_states(SoupState* out) override { std::memcpy(out, state_.data(), state_.size() * sizeof(SoupState)); }
     void do_fetch_board(i64 soup, u64* split) override {
         std::memcpy(split, board_.data() + (size_t)(soup * wps_), (size_t)wps_ * sizeof(u64));
+    }
+    void do_read_cells(i64 first, i64 count, const CellBuffer& dst) override {
+        unpack_cells_host(soup_source(board_.data(), first, count), dst);
+    }
+    void do_init_cells(const CellBuffer& src) override {
+        pack_cells_host(src, soup_target(board_.data()));
+        reset_states();
     }
 
    private:

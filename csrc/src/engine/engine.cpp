@@ -804,6 +804,95 @@ void Engine::stamp(const RlePattern& p, i64 r0, i64 c0, StampMode mode) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Dense cells: the tensor readers and writers (gol/cells.hpp; the backends convert)
+// ---------------------------------------------------------------------------------------------
+
+namespace {
+void need_cells(const CellBuffer& b, i64 cells, const char* what) {
+    if (b.numel != cells)
+        throw Error(strprintf("%s: the buffer holds %lld elements, the cells are %lld", what, (long long)b.numel, (long long)cells));
+}
+}  // namespace
+
+CellSource Engine::tile_source(const u64* buf, i64 r0, i64 c0, i64 rows, i64 cols) const {
+    CellSource s;
+    s.base = buf + L_.index(0, 0);
+    s.words = L_.words() - L_.index(0, 0);
+    s.frame_stride = 0, s.row_stride = L_.pitch;
+    s.n = 1, s.rows = rows, s.cols = cols;
+    s.r0 = pmod(r0, L_.h), s.H = L_.h;
+    s.c0 = pmod(c0, L_.w), s.W = L_.w;
+    s.w0 = 0, s.gwords = L_.nw, s.fw = L_.nw;
+    return s;
+}
+
+CellSource Engine::film_source(const u64* frames, i64 words, i64 n) const {
+    const FilmGeo& f = film_geo_;
+    CellSource s;
+    s.base = frames;
+    s.words = words;
+    s.frame_stride = f.slot_words(), s.row_stride = f.fw;
+    s.n = n, s.rows = f.rows, s.cols = f.cols;
+    s.r0 = 0, s.H = f.rows;
+    s.c0 = f.c0, s.W = f.W;
+    s.w0 = f.w0, s.gwords = f.gwords, s.fw = f.fw;
+    return s;
+}
+
+void Engine::read_tile_cells(const CellBuffer& dst) {
+    need_cells(dst, L_.h * L_.w, "read_tile_cells()");
+    check_cell_pointer(dst, "read_tile_cells()");
+    read_rect_cells(0, 0, L_.h, L_.w, dst);
+}
+
+void Engine::read_envelope_cells(const CellBuffer& dst) {
+    need_envelope("read_envelope_cells()");
+    need_cells(dst, L_.h * L_.w, "read_envelope_cells()");
+    check_cell_pointer(dst, "read_envelope_cells()");
+    ViewEnvelope v(view_env_);
+    read_rect_cells(0, 0, L_.h, L_.w, dst);
+}
+
+void Engine::write_tile_cells(const CellBuffer& src) {
+    need_cells(src, L_.h * L_.w, "write_tile_cells()");
+    check_cell_pointer(src, "write_tile_cells()");
+    write_tile_cells_local(src);
+    if (cfg_.envelope) envelope_reset();
+}
+
+void Engine::read_window_cells(i64 r0, i64 c0, i64 rows, i64 cols, const CellBuffer& dst) {
+    if (t_->size() > 1)
+        throw Error(strprintf("read_window_cells(): this job has %d ranks; a window is unpacked on the device for one rank "
+                              "only (use window())", t_->size()));
+    check_window(r0, c0, rows, cols);
+    need_cells(dst, rows * cols, "read_window_cells()");
+    check_cell_pointer(dst, "read_window_cells()");
+    read_rect_cells(r0, c0, rows, cols, dst);  // (one rank: the tile is the board)
+}
+
+void Engine::run_film_cells(u64 generations, const CellBuffer& dst) {
+    if (!cfg_.film.on)
+        throw Error("run_film_cells(): this engine is not in film mode (EngineConfig::film, Simulation(film=(r0, c0, rows, cols)), GOL_FILM=r0,c0,rows,cols)");
+    if (t_->size() > 1)
+        throw Error(strprintf("run_film_cells(): this job has %d ranks; frames are unpacked on the device for one rank only "
+                              "(use run() and film())", t_->size()));
+    const size_t held = film_frames();
+    if (held != 0)
+        throw Error(strprintf("run_film_cells(): the film record holds %zu frames; call film_clear() first", held));
+    const i64 per = film_geo_.rows * film_geo_.cols;
+    if (generations > (u64)(((i64)1 << 52) / per)) throw Error("run_film_cells(): more than 2^52 cells");
+    need_cells(dst, (i64)generations * per, "run_film_cells()");
+    if (generations > 0) check_cell_pointer(dst, "run_film_cells()");
+    for (u64 done = 0; done < generations;) {
+        const u64 n = std::min<u64>(generations - done, film_chunk());
+        run(n);
+        film_drain_cells((size_t)n, dst, (size_t)done);
+        done += n;
+    }
+    census_restart(gen_);
+}
+
+// ---------------------------------------------------------------------------------------------
 // CPU backend
 // ---------------------------------------------------------------------------------------------
 
@@ -889,6 +978,30 @@ class CpuEngine : public Engine {
     }
 
    protected:
+    // dense cells: host memory, host loops (gol/cells.hpp)
+    void check_cell_pointer(const CellBuffer&, const char*) override {}
+    void read_rect_cells(i64 r0, i64 c0, i64 rows, i64 cols, const CellBuffer& dst) override {
+        unpack_cells_host(tile_source(view_buf(), r0, c0, rows, cols), dst);
+    }
+    void write_tile_cells_local(const CellBuffer& src) override {
+        CellTarget t;
+        t.base = cur_ + L_.index(0, 0);
+        t.words = L_.words() - L_.index(0, 0);
+        t.row_stride = L_.pitch, t.rows = L_.h, t.cols = L_.w;
+        pack_cells_host(src, t);
+        refresh_local(cur_);
+    }
+    size_t film_chunk() const override {  // (the host record between two drains stays below 64 MiB)
+        return std::max<size_t>(8, ((size_t)64 << 20) / ((size_t)film_geo_.slot_words() * sizeof(u64)));
+    }
+    void film_drain_cells(size_t frames, const CellBuffer& dst, size_t at) override {
+        const i64 per = film_geo_.rows * film_geo_.cols;
+        if (film_host_.size() != frames * (size_t)film_geo_.slot_words()) throw Error("run_film_cells(): the record is not the chunk's");
+        CellBuffer part{(u8*)dst.ptr + at * (size_t)(per * cell_size(dst.type)), dst.type, (i64)frames * per};
+        unpack_cells_host(film_source(film_host_.data(), (i64)film_host_.size(), (i64)frames), part);
+        film_host_.clear();
+    }
+
     void do_init(const PatternSpec& p) override {
         cpu::init_tile(cur_, L_, g_, p);
         std::fill(oth_, oth_ + L_.words(), 0);

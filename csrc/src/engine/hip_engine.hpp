@@ -118,6 +118,13 @@ class HipEngine : public Engine {
     void density_local(i64 block_rows, i64 block_cols, u32* counts) override;
     void stamp_local(const RlePattern& p, i64 r0, i64 c0, StampMode mode) override;
 
+    // dense cells on the device (engine_hip_cells.hip; kernels: src/hip/tensor_kernels.hip)
+    void check_cell_pointer(const CellBuffer& b, const char* what) override;
+    void read_rect_cells(i64 r0, i64 c0, i64 rows, i64 cols, const CellBuffer& dst) override;
+    void write_tile_cells_local(const CellBuffer& src) override;
+    size_t film_chunk() const override { return film_cap_; }
+    void film_drain_cells(size_t frames, const CellBuffer& dst, size_t at) override;
+
     std::pair<u64, u64> local_reduce() override {
         sync_canonical();
         check_res_status();

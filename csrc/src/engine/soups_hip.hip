@@ -2,6 +2,7 @@
 // step_soups (src/hip/soup_kernel.hip).  One stream; after every settle / transient launch the host reads one counter,
 // so launches never queue up unbounded.
 #include "../hip/soup_kernel.hpp"
+#include "../hip/tensor_kernels.hpp"
 #include "gol/engine.hpp"
 #include "hip_engine.hpp"
 
@@ -86,6 +87,22 @@ class HipSoups final : public SoupBatch {
         const size_t one = (size_t)wps_ * sizeof(u64);
         HIP_CHECK(hipMemcpyAsync(split, board_ + (size_t)soup * (size_t)wps_, one, hipMemcpyDeviceToHost, stream_));
         HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    // dense cells on the device (tensor_kernels.hip): the caller's pointer is verified before anything is launched
+    void do_read_cells(i64 first, i64 count, const CellBuffer& dst) override {
+        use();
+        hipk::require_device_pointer(dst.ptr, (size_t)(dst.numel * cell_size(dst.type)), cfg_.device, "soups: read_boards_cells()");
+        hipk::launch_cells_from_words(soup_source(board_, first, count), dst, stream_);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+    void do_init_cells(const CellBuffer& src) override {
+        use();
+        hipk::require_device_pointer(src.ptr, (size_t)(src.numel * cell_size(src.type)), cfg_.device, "soups: init_cells()");
+        hipk::launch_words_from_cells(src, soup_target(board_), stream_);
+        HIP_CHECK(hipGetLastError());
+        hipk::launch_reset_soup_states(state_, (u32)cfg_.n, stream_);
+        reset();
     }
 
    private:

@@ -372,6 +372,92 @@ class Simulation:
             raise ValueError(f"expected a {(self.geometry.h, self.geometry.w)} board, got {cells.shape}")
         self.engine.set_tile_words(pack_cells(cells))
 
+    # -- torch tensors (ops/tensors.py states the dtypes and the stream ordering) ----------------
+    # On the HIP backend every tensor argument and result is a CUDA tensor on cuda:<device> and the cells never leave the
+    # device (kernels: tensor_kernels.hip); on the CPU backend they are CPU tensors.  ``dtype``: torch.bool, uint8 (the
+    # default), float16, bfloat16 or float32; ``out``: a contiguous tensor of the result's shape to fill instead of a new
+    # one (it is returned).  Before the engine touches a CUDA tensor the current torch stream of its device is
+    # synchronised; the engine synchronises its own stream before the call returns.  Argument errors are ValueErrors,
+    # raised before anything is launched.
+    def _tensor_device(self):
+        from ..ops import tensors
+
+        return tensors.device_of(self.backend, self.config.device)
+
+    def _one_rank(self, what: str) -> None:
+        P = self.transport.size()
+        if P > 1:
+            raise ValueError(f"{what}: this job has {P} ranks; the device-side {what} is built for one rank")
+
+    def board_tensor(self, dtype=None, out=None):
+        """This rank's tile as an ``(h, w)`` tensor of 0 and 1: :meth:`board` without the host.  Any rank count; no
+        communication.  The current torch stream is synchronised before the engine writes the tensor, and the engine's
+        stream before the call returns."""
+        from ..ops import tensors
+
+        t = tensors.result((self.geometry.h, self.geometry.w), dtype, self._tensor_device(), out, "board_tensor")
+        tensors.sync(t)
+        self.engine.read_tile_cells(*tensors.handle(t))
+        return t
+
+    def load_tensor(self, cells) -> "Simulation":
+        """:meth:`set_board` from an ``(h, w)`` tensor: a cell is alive iff its element ``!= 0`` (2, -1, 0.5 and NaN are
+        alive, ``-0.0`` is dead).  Any rank count; ghosts, halos and the envelope follow as after :meth:`set_board`.  The
+        current torch stream is synchronised before the engine reads the tensor."""
+        from ..ops import tensors
+
+        t = tensors.check_input(cells, (self.geometry.h, self.geometry.w), self._tensor_device(), "load_tensor")
+        tensors.sync(t)
+        self.engine.write_tile_cells(*tensors.handle(t))
+        return self
+
+    def envelope_tensor(self, dtype=None, out=None):
+        """``(start, cells)`` as :meth:`envelope` returns them, ``cells`` an ``(h, w)`` tensor.  Needs ``envelope=True``.
+        Stream ordering as :meth:`board_tensor`."""
+        from ..ops import tensors
+
+        self._need_envelope("envelope_tensor()")
+        t = tensors.result((self.geometry.h, self.geometry.w), dtype, self._tensor_device(), out, "envelope_tensor")
+        tensors.sync(t)
+        start = self.engine.read_envelope_cells(*tensors.handle(t))
+        return int(start), t
+
+    def window_tensor(self, r0: int, c0: int, rows: int, cols: int, dtype=None, out=None):
+        """:meth:`window` as a ``(rows, cols)`` tensor: same coordinates, wrapping and bounded-board checks.  One rank
+        only (more raise, naming the rank count).  Stream ordering as :meth:`board_tensor`."""
+        from ..ops import tensors
+
+        r0, c0, rows, cols = int(r0), int(c0), int(rows), int(cols)
+        self._one_rank("window_tensor")
+        H, W = self.decomposition.H, self.decomposition.W
+        if not (1 <= rows <= H and 1 <= cols <= W):
+            raise ValueError(f"window_tensor: a window of {rows} x {cols} cells: rows must be in 1..{H} and columns in 1..{W} (the board)")
+        self._check_inside("window_tensor", r0, c0, rows, cols)
+        t = tensors.result((rows, cols), dtype, self._tensor_device(), out, "window_tensor")
+        tensors.sync(t)
+        self.engine.read_window_cells(r0, c0, rows, cols, *tensors.handle(t))
+        return t
+
+    def step_film(self, generations: int, dtype=None, out=None):
+        """``generations`` generations whose frames go straight into a ``(generations, rows, cols)`` tensor ``f``:
+        ``f[i]`` is the film window at generation ``g0 + 1 + i``, ``g0`` the generation before the call; what
+        ``step(generations); film()`` returns, unpacked where the kernel stored it.  Needs ``film=...``, one rank and an
+        empty film record (call :meth:`film_clear` first, otherwise a ValueError); afterwards the record is empty and
+        starts at the generation reached, as after :meth:`film_clear`.  Stream ordering as :meth:`board_tensor`."""
+        from ..ops import tensors
+
+        generations = int(generations)
+        if self.config.film is None:
+            raise ValueError("step_film() needs a simulation built with film=(r0, c0, rows, cols) (or GOL_FILM)")
+        self._one_rank("step_film")
+        if generations < 0:
+            raise ValueError(f"step_film: generations = {generations} is negative")
+        _, _, rows, cols = self.config.film
+        t = tensors.result((generations, rows, cols), dtype, self._tensor_device(), out, "step_film")
+        tensors.sync(t)
+        self.engine.run_film_cells(generations, *tensors.handle(t))  # (a non-empty record: ValueError, nothing has run)
+        return t
+
     def population(self) -> int:
         """Global live-cell count (collective)."""
         return int(self.engine.population())

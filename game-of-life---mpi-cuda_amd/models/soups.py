@@ -35,15 +35,17 @@ class SoupBatch:
     """
 
     def __init__(self, n: int, size: int = 64, rule: str = "B3/S23", backend: str = "hip", seed: int = 0, device: int = 0, *,
-                 boundary: str = "torus", compat: bool = False, workgroup: int = 0, _boards=None):
+                 boundary: str = "torus", compat: bool = False, workgroup: int = 0, _boards=None, _tensor=None):
         n, size = int(n), int(size)
         if size not in SIZES:
             raise ValueError(f"soups: size {size} is not supported (a soup is a square torus of side 64, 128 or 256)")
         if not 1 <= n <= MAX_SOUPS:
             raise ValueError(f"soups: n = {n} is outside 1 .. 2^20")
         self._native = _gol.SoupBatch(n, size, str(rule), str(backend), int(device), str(boundary), bool(compat), int(workgroup))
-        self.n, self.size, self.backend = n, size, str(backend)
-        if _boards is None:
+        self.n, self.size, self.backend, self.device = n, size, str(backend), int(device)
+        if _tensor is not None:
+            self._native.init_cells(*_tensor)
+        elif _boards is None:
             self._native.init_seed(int(seed) & ((1 << 64) - 1))
         else:
             self._native.init_boards(_boards)
@@ -58,6 +60,54 @@ class SoupBatch:
         if bad.any():
             raise ValueError(f"soups: a board cell is {b[bad].flat[0].item()!r}, not 0 or 1")
         return cls(b.shape[0], b.shape[1], rule, backend, 0, device, _boards=np.ascontiguousarray(b, dtype=np.uint8), **kw)
+
+    @classmethod
+    def from_tensor(cls, boards, rule: str = "B3/S23", **kw) -> "SoupBatch":
+        """A batch of the ``(n, S, S)`` torch tensor ``boards``, one soup per board, a cell alive iff its element ``!= 0``
+        (dtypes and stream ordering: :mod:`gol_amd.ops.tensors`).  The backend follows the tensor: a CUDA tensor makes a
+        ``hip`` batch on its device and is packed there by a kernel, a CPU tensor a ``cpu`` batch; a ``backend`` or
+        ``device`` keyword that says otherwise is a ValueError."""
+        from ..ops import tensors
+
+        torch = tensors._torch()
+        if not isinstance(boards, torch.Tensor):
+            raise ValueError(f"soups: from_tensor expected a torch.Tensor, got {type(boards).__name__}")
+        if boards.dim() != 3 or boards.shape[1] != boards.shape[2]:
+            raise ValueError(f"soups: a tensor of shape {tuple(boards.shape)} is not (n, S, S)")
+        if boards.device.type not in ("cuda", "cpu"):
+            raise ValueError(f"soups: a tensor on {boards.device} is neither a CUDA nor a CPU tensor")
+        backend = "hip" if boards.is_cuda else "cpu"
+        device = boards.device.index if boards.is_cuda else 0
+        if kw.get("backend", backend) != backend:
+            raise ValueError(f"soups: a tensor on {boards.device} makes a {backend} batch, the call asks for backend {kw['backend']!r}")
+        if boards.is_cuda and int(kw.get("device", device)) != device:
+            raise ValueError(f"soups: the tensor is on {boards.device}, the call asks for device {kw['device']}")
+        kw.pop("backend", None)
+        kw.pop("device", None)
+        tensors.dtype_code(boards.dtype, "soups: from_tensor")
+        n, size = int(boards.shape[0]), int(boards.shape[1])
+        if size not in SIZES:  # (before the tensor is made contiguous or anything else is touched)
+            raise ValueError(f"soups: size {size} is not supported (a soup is a square torus of side 64, 128 or 256)")
+        if not 1 <= n <= MAX_SOUPS:
+            raise ValueError(f"soups: n = {n} is outside 1 .. 2^20")
+        t = boards.contiguous()
+        tensors.sync(t)
+        return cls(n, size, rule, backend, 0, device, _tensor=tensors.handle(t), **kw)
+
+    def boards_tensor(self, indices: Optional[Sequence[int]] = None, dtype=None, out=None):
+        """The boards of the soups ``indices`` as a ``(k, S, S)`` tensor of 0 and 1 on the batch's side (``hip``: a CUDA
+        tensor on the batch's device, unpacked there by a kernel; ``cpu``: a CPU tensor).  ``indices``: ``None`` (all) or a
+        contiguous range (``range(a, b)`` or a sequence that spells one out); anything else is a ValueError, as is a
+        wrong ``out`` (shape, dtype, contiguity, device).  The current torch stream is synchronised before the batch
+        writes the tensor; the batch synchronises its stream before the call returns (a pending :meth:`step` included)."""
+        from ..ops import tensors
+
+        first, count = tensors.index_range(indices, self.n, "soups: boards_tensor")
+        t = tensors.result((count, self.size, self.size), dtype, tensors.device_of(self.backend, self.device), out,
+                           "soups: boards_tensor")
+        tensors.sync(t)
+        self._native.read_boards_cells(first, count, *tensors.handle(t))
+        return t
 
     def step(self, generations: int = 1) -> "SoupBatch":
         """``generations`` steps of every soup, with no comparison.  Refused once :meth:`settle` has begun a search (the

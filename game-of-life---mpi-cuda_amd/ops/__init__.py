@@ -22,6 +22,7 @@ from .oracle import (  # noqa: F401
     torch_step_rule,
 )
 from .cycle import Cycle, find_repeat  # noqa: F401
+from .tensors import evolve  # noqa: F401
 from .rle import parse_rle, pattern_cells, pattern_from_cells, write_rle  # noqa: F401
 from .._native import _gol as _native
 
