@@ -207,6 +207,8 @@ struct ResidentParams {
     i32 kmax;    // halo rows of the tiles: >= ceil(G / S)
     u64 timeout_ticks;  // bound of every neighbour wait, in s_memrealtime ticks (100 MHz)
 };
+// Instantiated: 16 waves x B in {2, 3, 4, 5, 6, 8} and 8 waves x B in {3, 4, 5, 6, 8, 10, 12, 16}, the tile its own
+// N/S neighbour (wrapy); anything else throws "no kernel for ...".
 int resident_band_rows(int rows_needed);  // supported band height >= rows_needed (0: none)
 int resident_blocks_per_cu(int nw, int B, bool wrapy);
 void launch_step_resident(int nw, int B, bool wrapy, u64* src, u64* dst, const LaneDesc* plan, i64 n_tiles,

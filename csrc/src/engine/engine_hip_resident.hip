@@ -15,19 +15,42 @@ const HipEngine::ResPlan& HipEngine::res_plan(int kin) {
     rp.kin = kin;
     const std::vector<Region> rg = {{0, L_.h, 0, L_.nw}};
     const bool wrapy = true;  // resident_eligible(): the rank is its own N/S neighbour
+    // GOL_RESIDENT=tiles,nw (test knob): plan as for a card of `tiles` CUs (clamped to 1 .. the card's: never
+    // more tiles than can be co-resident, whose waits would only time out) with `nw` waves per tile, so that a
+    // small board gets tall tiles and any band height.  The planner counts a plan in whole blocks of four waves,
+    // so below four `tiles` no height fits and the plan is one band; the co-residency test then counts the
+    // tiles that have rows (a padding tile exits at once).
+    i64 cus = cus_;
+    int nw = 16;
+    const std::string knob = env_str("GOL_RESIDENT", "");
+    if (!knob.empty()) {
+        long long t = 0;
+        int n = 0;
+        char tail = 0;
+        if (sscanf(knob.c_str(), "%lld,%d%c", &t, &n, &tail) != 2 || t < 1 || (n != 8 && n != 16))
+            throw Error("GOL_RESIDENT must be tiles,nw with tiles >= 1 and nw 8 or 16 (got '" + knob + "')");
+        cus = std::min<i64>(t, cus_);
+        nw = n;
+    }
+    rp.nw = nw;
     for (int per_cu : {1, 2}) {
-        const int bmax = per_cu == 1 ? 8 : 4;
-        const i64 rows = balanced_rows_per_chunk(rg, L_.nw, L_.h, kin, (i64)per_cu * cus_, 1, true);
-        if (rows + 2 * (i64)kin > 16 * (i64)bmax) continue;
-        const int B = hipk::resident_band_rows((int)ceil_div(rows + 2 * (i64)kin, 16));
+        const int bmax = (per_cu == 1 ? 128 : 64) / nw;  // tiles of at most 128 / 64 extended rows
+        const i64 rows = balanced_rows_per_chunk(rg, L_.nw, L_.h, kin, (i64)per_cu * cus, 1, true);
+        if (rows + 2 * (i64)kin > nw * (i64)bmax) continue;
+        const int B = hipk::resident_band_rows((int)ceil_div(rows + 2 * (i64)kin, nw));
         if (B <= 0 || B > bmax) continue;
-        if (hipk::resident_blocks_per_cu(16, B, wrapy) < per_cu) continue;
+        if (hipk::resident_blocks_per_cu(nw, B, wrapy) < per_cu) continue;
         std::vector<LaneDesc> lanes = build_plan(rg, L_.nw, L_.h, rows, kin, true, nullptr, 1, cfg_.plan_xcds);
         const i64 tiles = (i64)lanes.size() / kWaveLanes;
-        if (tiles > (i64)per_cu * cus_) continue;  // all tiles must be co-resident
+        i64 live = tiles;
+        if (!knob.empty()) {
+            live = 0;
+            for (size_t w = 0; w < (size_t)tiles; ++w) live += lanes[w * kWaveLanes].nrows > 0;
+        }
+        if (live > (i64)per_cu * cus) continue;  // all tiles must be co-resident
         i64 tallest = 0;
         for (size_t w = 0; w < (size_t)tiles; ++w) tallest = std::max<i64>(tallest, lanes[w * kWaveLanes].nrows);
-        if (tallest + 2 * (i64)kin > 16 * (i64)B) continue;
+        if (tallest + 2 * (i64)kin > nw * (i64)B) continue;
         std::string bad = validate_plan(lanes, L_.nw, L_.h, L_.R, kin, true);
         std::vector<u32> off, idx;
         if (bad.empty()) bad = resident_neighbours(lanes, L_.nw, L_.h, kin, true, off, idx);

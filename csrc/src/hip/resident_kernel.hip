@@ -65,7 +65,7 @@ __device__ __forceinline__ void store_sc1(u64* p, u64 v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int NW, int B, bool WRAPY>
+template <int NW, int B>
 __global__ __launch_bounds__(64 * NW) void step_resident(u64* __restrict__ src, u64* __restrict__ dst,
                                                          const LaneDesc* __restrict__ plan,
                                                          const u32* __restrict__ nbr_off,
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(64 * NW) void step_resident(u64* __restrict__ src, 
         int e;
         asm volatile("s_mov_b32 %0, %1" : "=s"(e) : "s"(e0));
         int r = d.row0 - K + e;
-        if (WRAPY) r = r < 0 ? r + rp.h : (r >= rp.h ? r - rp.h : r);
+        r = r < 0 ? r + rp.h : (r >= rp.h ? r - rp.h : r);  // the tile is its own N/S neighbour
         return buf + (i64)(r + rp.R) * rp.pitch + (d.col + 1);
     };
     u32 lo[B], hi[B];
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(64 * NW) void step_resident(u64* __restrict__ src, 
                 continue;
             }
             const Hs first = hs_of(lo[0], hi[0]);
-            const Hs last = B > 1 ? hs_of(lo[B - 1], hi[B - 1]) : first;
+            const Hs last = hs_of(lo[B - 1], hi[B - 1]);
             edge[par][wv][0][lane] = make_uint4(first.s0l, first.s1l, first.s0h, first.s1h);
             edge[par][wv][1][lane] = make_uint4(last.s0l, last.s1l, last.s0h, last.s1h);
             __syncthreads();
@@ -128,27 +128,23 @@ __global__ __launch_bounds__(64 * NW) void step_resident(u64* __restrict__ src, 
             if (wv > 0) ua = edge[par][wv - 1][1][lane];
             if (wv < NW - 1) ub = edge[par][wv + 1][0][lane];
             const Hs above{ua.x, ua.y, ua.z, ua.w}, below{ub.x, ub.y, ub.z, ub.w};
-            if constexpr (B == 1) {
-                rule_row(above, first, below, lo[0], hi[0]);
-            } else {
-                // interior rows 1 .. B-2 first (the neighbours' edge sums arrive meanwhile); every
-                // row's sums are taken from its old value before that row is overwritten
-                const Hs h1 = B > 2 ? hs_of(lo[1], hi[1]) : last;  // sums of row 1
-                Hs prev = first, cur = h1;
+            // interior rows 1 .. B-2 first (the neighbours' edge sums arrive meanwhile); every row's
+            // sums are taken from its old value before that row is overwritten
+            const Hs h1 = B > 2 ? hs_of(lo[1], hi[1]) : last;  // sums of row 1
+            Hs prev = first, cur = h1;
 #pragma unroll
-                for (int i = 1; i + 1 < B; ++i) {
-                    const Hs nx = i + 2 < B ? hs_of(lo[i + 1], hi[i + 1]) : last;
-                    rule_row(prev, cur, nx, lo[i], hi[i]);
-                    prev = cur;
-                    cur = nx;
-                    // one row at a time: hoisting every row's sums above the rules would hold 4 x B
-                    // more VGPRs
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                const Hs hb2 = B > 2 ? prev : first;  // sums of row B-2
-                rule_row(above, first, h1, lo[0], hi[0]);
-                rule_row(hb2, last, below, lo[B - 1], hi[B - 1]);
+            for (int i = 1; i + 1 < B; ++i) {
+                const Hs nx = i + 2 < B ? hs_of(lo[i + 1], hi[i + 1]) : last;
+                rule_row(prev, cur, nx, lo[i], hi[i]);
+                prev = cur;
+                cur = nx;
+                // one row at a time: hoisting every row's sums above the rules would hold 4 x B more
+                // VGPRs
+                __builtin_amdgcn_sched_barrier(0);
             }
+            const Hs hb2 = B > 2 ? prev : first;  // sums of row B-2
+            rule_row(above, first, h1, lo[0], hi[0]);
+            rule_row(hb2, last, below, lo[B - 1], hi[B - 1]);
         }
         // ---- superstep end: publish the output rows (extended rows K .. K+nrows-1) ----
         // (rp.S is odd: supersteps S, S-2, ... write dst, the others src; the first writes dst)
@@ -205,33 +201,31 @@ __global__ __launch_bounds__(64 * NW) void step_resident(u64* __restrict__ src, 
     }
 }
 
-template <int NW, int B>
-const void* resident_kernel_wrap(bool wrapy) {
-    return wrapy ? (const void*)step_resident<NW, B, true> : (const void*)step_resident<NW, B, false>;
-}
-
-template <int NW>
-const void* resident_kernel_nw(int B, bool wrapy) {
-    switch (B) {
-        case 2: return resident_kernel_wrap<NW, 2>(wrapy);
-        case 3: return resident_kernel_wrap<NW, 3>(wrapy);
-        case 4: return resident_kernel_wrap<NW, 4>(wrapy);
-        case 5: return resident_kernel_wrap<NW, 5>(wrapy);
-        case 6: return resident_kernel_wrap<NW, 6>(wrapy);
-        case 8: return resident_kernel_wrap<NW, 8>(wrapy);
-        case 10: return resident_kernel_wrap<NW, 10>(wrapy);
-        case 12: return resident_kernel_wrap<NW, 12>(wrapy);
-        case 16: return resident_kernel_wrap<NW, 16>(wrapy);
-        default: return nullptr;
-    }
-}
-
-const void* resident_kernel(int nw, int B, bool wrapy) {
-    switch (nw) {
-        case 8: return resident_kernel_nw<8>(B, wrapy);
-        case 16: return resident_kernel_nw<16>(B, wrapy);
-        default: return nullptr;
-    }
+// The variants the planner can pick (engine_hip_resident.hip res_plan; tests/resident_cases.py derives the
+// table from its arithmetic): tiles hold at most 128 extended rows, at least 2 x 8 + 1, so 16 waves keep
+// bands of 2 .. 8 rows and 8 waves bands of 3 .. 16.
+const void* resident_kernel(int nw, int B) {
+    if (nw == 16) switch (B) {
+            case 2: return (const void*)step_resident<16, 2>;
+            case 3: return (const void*)step_resident<16, 3>;
+            case 4: return (const void*)step_resident<16, 4>;
+            case 5: return (const void*)step_resident<16, 5>;
+            case 6: return (const void*)step_resident<16, 6>;
+            case 8: return (const void*)step_resident<16, 8>;
+            default: return nullptr;
+        }
+    if (nw == 8) switch (B) {
+            case 3: return (const void*)step_resident<8, 3>;
+            case 4: return (const void*)step_resident<8, 4>;
+            case 5: return (const void*)step_resident<8, 5>;
+            case 6: return (const void*)step_resident<8, 6>;
+            case 8: return (const void*)step_resident<8, 8>;
+            case 10: return (const void*)step_resident<8, 10>;
+            case 12: return (const void*)step_resident<8, 12>;
+            case 16: return (const void*)step_resident<8, 16>;
+            default: return nullptr;
+        }
+    return nullptr;
 }
 
 size_t resident_lds_bytes(int nw) { return (size_t)(2 * nw * 2 * 64 + 1) * sizeof(uint4); }
@@ -239,7 +233,8 @@ size_t resident_lds_bytes(int nw) { return (size_t)(2 * nw * 2 * 64 + 1) * sizeo
 // the kernel's dynamic LDS exceeds the 64 KiB default at 16 waves: raise the limit once per
 // (device, kernel variant)
 const void* resident_kernel_checked(int nw, int B, bool wrapy) {
-    const void* f = resident_kernel(nw, B, wrapy);
+    if (!wrapy) throw Error(strprintf("step_resident: no kernel for %d waves x %d band rows without y-wrap", nw, B));
+    const void* f = resident_kernel(nw, B);
     if (!f) throw Error(strprintf("step_resident: no kernel for %d waves x %d band rows", nw, B));
     static std::mutex mu;
     static std::set<std::pair<int, const void*>> done;

@@ -476,13 +476,33 @@ static void test_resident() {
     struct Case {
         i64 h, nw, rows;
         int K, NW, B, G;
+        bool fill = false;  // rows + 2 K = NW x B
     };
     for (const Case& c : std::vector<Case>{{96, 2, 24, 4, 8, 5, 13},
                                            {96, 2, 24, 4, 8, 5, 12},
-                                           {80, 1, 10, 3, 4, 4, 9},
+                                           {80, 1, 10, 3, 8, 3, 9},
                                            {128, 3, 32, 8, 8, 6, 40},
                                            {64, 2, 64, 6, 8, 10, 17},
-                                           {70, 70, 20, 5, 8, 4, 31}}) {
+                                           {70, 70, 20, 5, 8, 4, 31},
+                                           // every (NW, B) the kernel dispatches, the tile filling NW x B exactly
+                                           // (rows + 2 K = NW x B, G = 3 K: three full supersteps); two bands, or
+                                           // one tile that reloads its own rows
+                                           {32, 1, 16, 8, 16, 2, 24, true},
+                                           {64, 1, 32, 8, 16, 3, 24, true},
+                                           {80, 1, 40, 12, 16, 4, 36, true},
+                                           {64, 2, 64, 8, 16, 5, 24, true},
+                                           {128, 1, 64, 16, 16, 6, 48, true},
+                                           {80, 1, 80, 24, 16, 8, 72, true},
+                                           {16, 1, 8, 8, 8, 3, 24, true},
+                                           {32, 2, 16, 8, 8, 4, 24, true},
+                                           {32, 1, 16, 12, 8, 5, 36, true},
+                                           {64, 1, 32, 8, 8, 6, 24, true},
+                                           {64, 1, 32, 16, 8, 8, 48, true},
+                                           {64, 1, 64, 8, 8, 10, 24, true},
+                                           {96, 1, 48, 24, 8, 12, 72, true},
+                                           {112, 63, 112, 8, 8, 16, 24, true}}) {
+        CHECK(c.rows + 2 * c.K <= c.NW * c.B);
+        if (c.fill) CHECK(c.h % c.rows == 0 && c.rows + 2 * c.K == c.NW * c.B && c.G == 3 * c.K);
         const i64 W = c.nw * 64;
         auto b = random_board(c.h, W, (unsigned)(c.h * 7 + c.nw + c.G));
         std::vector<u8> ref = b;

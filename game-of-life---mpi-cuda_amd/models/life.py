@@ -56,8 +56,8 @@ class Simulation:
                   generations runs as several kernel passes in 1-D (communication-avoiding halos).
     kernel:       HIP stencil kernel: ``"auto"`` (candidates timed at init), ``"temporal"``,
                   ``"tile"``, ``"pipe"`` (level-pipelined workgroups; geometry GOL_PIPE=nw,L,wg),
-                  ``"resident"``, ``"lds"`` or ``"rule"`` (the generic rule kernel, also for B3/S23;
-                  GOL_KERNEL).
+                  ``"resident"`` (test knob GOL_RESIDENT=tiles,nw: plan as for ``tiles`` CUs, 8 or 16 waves per
+                  tile), ``"lds"`` or ``"rule"`` (the generic rule kernel, also for B3/S23; GOL_KERNEL).
     decomp/grid:  ``"1d"`` row strips (reference) or ``"2d"`` blocks, optional ``"PxxPy"`` grid.
     width:        board columns (0 = N: the reference's square tiles).  With ``width`` the per-rank
                   strip (or, in global mode, the board) is N rows x ``width`` columns.

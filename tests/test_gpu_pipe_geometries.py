@@ -17,8 +17,8 @@ supersteps and a one-generation step_temporal remainder.  A wrong board fails wi
                               supersteps of two passes (the first stores the ghost rows the second reads); a 2 x 2 grid
                               (ghost words stored too).
 
-The split schedule (its interior kernel is chosen by timing, so it cannot be pinned) and the resident kernel are not
-covered here."""
+The split schedule (its interior kernel is chosen by timing, so it cannot be pinned) is not covered here; the resident
+kernel has its own every-variant file, test_gpu_resident_variants.py."""
 import pytest
 
 import pipe_cases as pc
