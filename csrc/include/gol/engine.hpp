@@ -27,6 +27,7 @@
 #include "gol/density_film.hpp"
 #include "gol/film.hpp"
 #include "gol/geometry.hpp"
+#include "gol/match.hpp"
 #include "gol/pattern.hpp"
 #include "gol/plan.hpp"
 #include "gol/rle.hpp"
@@ -138,6 +139,7 @@ struct EngineStats {
     std::string tuning;        // init-time measurements behind the auto choices (HIP)
     bool registered = false;   // HIP + RCCL: the boards are registered with the communicator (zero-copy halos)
     u64 view_bytes_d2h = 0;    // HIP: bytes window() copied from the device (this rank's cells of the windows)
+    u64 match_launches = 0;    // matcher runs of match() and match_cells(), one per oriented template (HIP: k_match launches)
 };
 
 // How stamp() combines a pattern with the board.  Replace overwrites the pattern's bounding rectangle;
@@ -288,6 +290,23 @@ class Engine {
     void check_density(i64 block_rows, i64 block_cols) const;
     void check_stamp(const RlePattern& p) const;
     void check_stamp(const RlePattern& p, i64 r0, i64 c0) const;
+    // ----- pattern matching (gol/match.hpp) -----
+    // Where the oriented templates `ts` ((orientation id, template), MatchTemplate::orientations) match on the current
+    // board, torus or bounded as the engine runs.  One rank only: more throw, naming the rank count, before anything is
+    // launched (the neighbours' rows would be needed).  Every template is validated against the board first, and
+    // max_hits < 1 is refused.  HIP: k_match writes a board-sized bitmap and a counter, k_match_positions compacts the
+    // bitmap; only the counter and the positions leave the device.
+    struct MatchResult {
+        u64 count = 0;                 // matches over all the templates of `ts`; always exact
+        std::vector<i32> positions;    // (row, col) pairs sorted by (row, col, orientation): all of them, or, with
+                                       // count > max_hits, some max_hits of them (truncated)
+        std::vector<u8> orientation;   // the id of each pair's template
+        bool truncated = false;
+    };
+    MatchResult match(const std::vector<std::pair<int, MatchTemplate>>& ts, i64 max_hits, bool positions);
+    // dst (h x w dense cells, as read_tile_cells takes them): 1 where any template of `ts` matches, else 0.
+    void match_cells(const std::vector<std::pair<int, MatchTemplate>>& ts, const CellBuffer& dst);
+
     // ----- dense cells: the tensor readers and writers (gol/cells.hpp) -----
     // The caller's buffer is one element per cell (u8, f16, bf16 or f32; exact 0 and 1 out, != 0 alive in).  HIP
     // backend: device memory of the engine's device, verified with hipPointerGetAttributes before anything is launched,
@@ -443,6 +462,14 @@ class Engine {
     virtual void write_tile_cells_local(const CellBuffer& src) = 0;
     virtual size_t film_chunk() const = 0;
     virtual void film_drain_cells(size_t frames, const CellBuffer& dst, size_t at) = 0;
+    // Pattern matching: the backends' parts.  match_local: run the matcher for one template on the current board and
+    // return its matches; with keep, the backend's bitmap then holds them (or_into: ORed into what it held).
+    // match_positions_local: `cap` (row, col) pairs of the bitmap's set bits (cap <= their number) appended to out.
+    // match_bitmap_cells: the bitmap as dense cells.
+    virtual u64 match_local(const MatchTemplate& t, bool keep, bool or_into) = 0;
+    virtual void match_positions_local(i64 cap, std::vector<i32>* out) = 0;
+    virtual void match_bitmap_cells(const CellBuffer& dst) = 0;
+    void check_match(const std::vector<std::pair<int, MatchTemplate>>& ts, const char* what) const;
 
     Geometry g_;
     EngineConfig cfg_;

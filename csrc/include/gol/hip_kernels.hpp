@@ -31,6 +31,7 @@
 //   copy_regions      — batched strided copies: 2-D halo pack/unpack and self-neighbour copies.
 //   reduce_board      — population + decomposition-invariant fingerprint.
 //   window_bytes / density / stamp — views of the live board and pattern stamping (view_kernels.hip).
+//   match / match_positions — template matching on the live board and on soup batches (match_kernel.hip).
 //   naive_byte_step   — byte-per-cell, thread-per-cell yardstick of the reference's algorithm class
 //                       (no printf), used only by the benchmark for comparison.
 #pragma once
@@ -41,6 +42,7 @@
 
 #include "gol/density_film.hpp"
 #include "gol/geometry.hpp"
+#include "gol/match.hpp"
 #include "gol/plan.hpp"
 #include "gol/rule.hpp"
 
@@ -275,6 +277,28 @@ void launch_density(const u64* buf, const Layout& L, i64 row0, i64 gword0, i64 b
 // whose cell (pr0, pc0) lands on the rectangle's first cell; mode 0 or, 1 replace, 2 xor, 3 clear.
 void launch_stamp(u64* buf, const Layout& L, const ViewRect& rc, const u64* pat, i64 pnw, i64 pr0, i64 pc0, int mode,
                   hipStream_t s);
+
+// ----- pattern matching (match_kernel.hip; gol/match.hpp) -----
+// Where the boards are: board b's word c of row r is at base + b * batch_stride + r * pitch + c (words), rows 0 .. h - 1,
+// words 0 .. nw - 1 = ceil(w / 64); nothing else is read.  The engine's board: match_geo(L, torus), i.e. base = R * pitch + 1,
+// one board.  A soup batch: base 0, pitch = nw, batch_stride = h * nw.
+struct MatchGeo {
+    i64 base = 0, pitch = 0, batch_stride = 0;
+    i64 w = 0;
+    i32 h = 0, nw = 0;
+    i32 torus = 1;  // 1: coordinates wrap; 0: cells outside the board are dead
+    i32 batch = 1;
+};
+MatchGeo match_geo(const Layout& L, bool torus);
+// k_match: for every word of every board the 64-bit bitmap of the cells at which `t` matches, in the board's split
+// format, stored at the word's own offset in `bitmap` (a buffer addressed like the boards; nullptr: not stored; or_into:
+// ORed into what is there), and the number of matches added to count32[b] (one u32 per board) or to count64[0] (one
+// board only); the caller zeroes the counters.  Validates the template against the board before the launch.
+void launch_match(const u64* board, const MatchGeo& g, const MatchTemplate& t, u64* bitmap, bool or_into, u32* count32,
+                  u64* count64, hipStream_t s);
+// k_match_positions: the set bits of board 0's bitmap as (row, col) pairs of i32 in no particular order: the first `cap`
+// to arrive are stored at out, and cursor[0] (zeroed by the caller) ends as the number of set bits.
+void launch_match_positions(const u64* bitmap, const MatchGeo& g, i32* out, i64 cap, u64* cursor, hipStream_t s);
 
 // Yardstick: one byte per cell, one thread per cell, x-wrap + two ghost rows (reference class).
 void launch_naive_byte_step(const u8* src, u8* dst, i64 w, i64 h, const u8* above, const u8* below, int threads,

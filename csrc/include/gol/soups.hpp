@@ -26,6 +26,7 @@
 
 #include "gol/cells.hpp"
 #include "gol/common.hpp"
+#include "gol/match.hpp"
 #include "gol/rule.hpp"
 
 namespace gol {
@@ -109,6 +110,11 @@ class SoupBatch {
     void read_boards_cells(i64 first, i64 count, const CellBuffer& dst);
     // init_words() from (n, S, S) elements, alive iff != 0.
     void init_cells(const CellBuffer& src);
+    // Pattern matching (gol/match.hpp): n x T counts, entry (i, t) the matches of the oriented templates templates[t],
+    // summed, on soup i's current board (a torus).  Every template is validated against the soup's size before anything
+    // runs.  HIP: the batch's stream is synchronised first (a pending step() is included), then one k_match launch per
+    // oriented template over all soups adds into one counter per soup; no bitmap is kept.
+    std::vector<u32> match_counts(const std::vector<std::vector<MatchTemplate>>& templates);
     SoupStats stats() const;
     // Waits for the launches of step() (HIP; every other call returns finished work).
     virtual void synchronize() {}
@@ -127,6 +133,8 @@ class SoupBatch {
     virtual void do_fetch_board(i64 soup, u64* split) = 0;
     virtual void do_read_cells(i64 first, i64 count, const CellBuffer& dst) = 0;
     virtual void do_init_cells(const CellBuffer& src) = 0;  // the boards and, as do_upload, the states
+    // counts[i] = the matches of the templates, summed, on soup i's board (n counts)
+    virtual void do_match_counts(const std::vector<MatchTemplate>& oriented, u32* counts) = 0;
     // the soups first .. first + count - 1 of a store of n x S x m words
     CellSource soup_source(const u64* store, i64 first, i64 count) const;
     CellTarget soup_target(u64* store) const;

@@ -142,7 +142,17 @@ py::dict stats_dict(const EngineStats& s) {
     d["tuning"] = s.tuning;
     d["registered"] = s.registered;
     d["view_bytes_d2h"] = s.view_bytes_d2h;
+    d["match_launches"] = s.match_launches;
     return d;
+}
+
+// a template's value or care cells as a (th, tw) uint8 array
+py::array_t<u8> template_cells(const MatchTemplate& t, bool care) {
+    py::array_t<u8> a({(py::ssize_t)t.th, (py::ssize_t)t.tw});
+    u8* p = a.mutable_data();
+    for (int i = 0; i < t.th; ++i)
+        for (int j = 0; j < t.tw; ++j) p[i * t.tw + j] = (u8)(care ? t.cell_care(i, j) : t.cell_value(i, j));
+    return a;
 }
 
 }  // namespace
@@ -580,6 +590,29 @@ PYBIND11_MODULE(_gol, m) {
         .def("run_film_cells", [](Engine& e, u64 generations, uintptr_t ptr, int code, i64 numel) {
             cells_call([&](const CellBuffer& b) { e.run_film_cells(generations, b); }, ptr, code, numel);
         })
+        // pattern matching (gol/match.hpp): ts = [(orientation id, MatchTemplate)]; (count, positions (k, 2) int64, orientation
+        // (k,) uint8, truncated); what a call refuses is a ValueError, raised before anything is launched
+        .def(
+            "match",
+            [](Engine& e, const std::vector<std::pair<int, MatchTemplate>>& ts, i64 max_hits, bool positions) {
+                Engine::MatchResult res;
+                try {
+                    py::gil_scoped_release r;
+                    res = e.match(ts, max_hits, positions);
+                } catch (const Error& err) {
+                    throw py::value_error(err.what());
+                }
+                const py::ssize_t k = (py::ssize_t)res.orientation.size();
+                py::array_t<i64> pos({k, (py::ssize_t)2});
+                py::array_t<u8> ids(k);
+                for (py::ssize_t i = 0; i < 2 * k; ++i) pos.mutable_data()[i] = res.positions[(size_t)i];
+                if (k) std::memcpy(ids.mutable_data(), res.orientation.data(), (size_t)k);
+                return py::make_tuple(res.count, pos, ids, res.truncated);
+            },
+            py::arg("templates"), py::arg("max_hits") = (i64)1 << 20, py::arg("positions") = true)
+        .def("match_cells", [](Engine& e, const std::vector<std::pair<int, MatchTemplate>>& ts, uintptr_t ptr, int code, i64 numel) {
+            cells_call([&](const CellBuffer& b) { e.match_cells(ts, b); }, ptr, code, numel);
+        })
         .def("device_barrier", &Engine::device_barrier, py::call_guard<py::gil_scoped_release>())
         .def("phase_probe", &Engine::phase_probe, py::arg("k"), py::call_guard<py::gil_scoped_release>())
         .def("time_runs", &Engine::time_runs, py::arg("gens"), py::arg("reps"), py::call_guard<py::gil_scoped_release>())
@@ -682,6 +715,50 @@ PYBIND11_MODULE(_gol, m) {
     });
     m.def("write_rle", &write_rle);
     m.def("write_rle_file", &write_rle_file);
+
+    // ---- match templates (gol/match.hpp) ------------------------------------------------------
+    // (what a builder or validate() refuses is a ValueError)
+    py::class_<MatchTemplate>(m, "MatchTemplate")
+        .def(py::init([](py::array_t<u8, py::array::c_style | py::array::forcecast> value,
+                         py::array_t<u8, py::array::c_style | py::array::forcecast> care, i64 ring) {
+                 if (value.ndim() != 2 || care.ndim() != 2 || value.shape(0) != care.shape(0) || value.shape(1) != care.shape(1))
+                     throw py::value_error("match: value and care must be 2-D arrays of one shape");
+                 try {
+                     MatchTemplate t = MatchTemplate::from_cells(value.data(), care.data(), value.shape(0), value.shape(1), ring);
+                     t.validate();
+                     return t;
+                 } catch (const Error& e) {
+                     throw py::value_error(e.what());
+                 }
+             }),
+             py::arg("value"), py::arg("care"), py::arg("ring") = 0)
+        .def_static(
+            "from_pattern",
+            [](const RlePattern& p, i64 margin) {
+                try {
+                    MatchTemplate t = MatchTemplate::from_pattern(p, margin);
+                    t.validate();
+                    return t;
+                } catch (const Error& e) {
+                    throw py::value_error(e.what());
+                }
+            },
+            py::arg("pattern"), py::arg("margin") = 1)
+        .def_readonly("th", &MatchTemplate::th)
+        .def_readonly("tw", &MatchTemplate::tw)
+        .def_readonly("ring", &MatchTemplate::ring)
+        .def_property_readonly("value", [](const MatchTemplate& t) { return template_cells(t, false); })
+        .def_property_readonly("care", [](const MatchTemplate& t) { return template_cells(t, true); })
+        .def("oriented",
+             [](const MatchTemplate& t, int k) {
+                 try {
+                     return t.oriented(k);
+                 } catch (const Error& e) {
+                     throw py::value_error(e.what());
+                 }
+             })
+        // [(id, template)]: orientation 0 alone, or all eight without duplicates
+        .def("orientations", [](const MatchTemplate& t, bool all) { return t.orientations(all); }, py::arg("all") = true);
 
     // ---- soup batches ---------------------------------------------------------------------
     // (what the configuration or a call refuses is a ValueError, like a bad rule string)
@@ -794,6 +871,20 @@ PYBIND11_MODULE(_gol, m) {
         .def("init_cells", [](SoupBatch& b, uintptr_t ptr, int code, i64 numel) {
             cells_call([&](const CellBuffer& c) { b.init_cells(c); }, ptr, code, numel);
         })
+        // (n, T) uint32: entry (i, t) the matches of the oriented templates templates[t], summed, on soup i's board
+        .def("match_counts",
+             [](SoupBatch& b, const std::vector<std::vector<MatchTemplate>>& templates) {
+                 std::vector<u32> counts;
+                 try {
+                     py::gil_scoped_release r;
+                     counts = b.match_counts(templates);
+                 } catch (const Error& e) {
+                     throw py::value_error(e.what());
+                 }
+                 py::array_t<u32> a({(py::ssize_t)b.n(), (py::ssize_t)templates.size()});
+                 if (!counts.empty()) std::memcpy(a.mutable_data(), counts.data(), counts.size() * sizeof(u32));
+                 return a;
+             })
         .def("synchronize",
              [](SoupBatch& b) {
                  py::gil_scoped_release r;

@@ -162,6 +162,21 @@ void SoupBatch::init_cells(const CellBuffer& src) {
     reached_ = launches_ = settled_ = 0;
 }
 
+std::vector<u32> SoupBatch::match_counts(const std::vector<std::vector<MatchTemplate>>& templates) {
+    for (const auto& oriented : templates) {
+        if (oriented.empty()) throw Error("soups: match_counts(): a template without orientations");
+        for (const MatchTemplate& t : oriented) t.validate(cfg_.size, cfg_.size);
+    }
+    const size_t T = templates.size();
+    std::vector<u32> out((size_t)cfg_.n * T, 0), col((size_t)cfg_.n);
+    for (size_t t = 0; t < T; ++t) {
+        std::fill(col.begin(), col.end(), 0u);
+        do_match_counts(templates[t], col.data());
+        for (i64 i = 0; i < cfg_.n; ++i) out[(size_t)i * T + t] = col[(size_t)i];
+    }
+    return out;
+}
+
 SoupStats SoupBatch::stats() const {
     SoupStats s;
     s.kernel = strprintf("soups@%lld", (long long)cfg_.size) + (cfg_.rule.is_conway() ? "" : ":rule");
@@ -357,6 +372,20 @@ class CpuSoups final : public SoupBatch {
     void do_init_cells(const CellBuffer& src) override {
         pack_cells_host(src, soup_target(board_.data()));
         reset_states();
+    }
+    void do_match_counts(const std::vector<MatchTemplate>& oriented, u32* counts) override {
+#pragma omp parallel
+        {
+            std::vector<u64> nat((size_t)wps_);
+#pragma omp for schedule(static)
+            for (i64 i = 0; i < cfg_.n; ++i) {
+                const u64* b = board_.data() + (size_t)(i * wps_);
+                for (i64 k = 0; k < wps_; ++k) nat[(size_t)k] = merge_word(b[k]);
+                u64 c = 0;
+                for (const MatchTemplate& t : oriented) c += match_host(nat.data(), cfg_.size, cfg_.size, true, t, nullptr);
+                counts[i] = (u32)c;
+            }
+        }
     }
 
    private:

@@ -893,6 +893,67 @@ void Engine::run_film_cells(u64 generations, const CellBuffer& dst) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Pattern matching (gol/match.hpp; the backends run the matcher)
+// ---------------------------------------------------------------------------------------------
+
+void Engine::check_match(const std::vector<std::pair<int, MatchTemplate>>& ts, const char* what) const {
+    if (t_->size() > 1)
+        throw Error(strprintf("%s: this job has %d ranks; matching is built for one rank (a tile's edge cells need the "
+                              "neighbours' rows)", what, t_->size()));
+    if (ts.empty()) throw Error(std::string(what) + ": no template");
+    for (const auto& e : ts) {
+        if (e.first < 0 || e.first > 7) throw Error(strprintf("%s: orientation id %d is outside 0 .. 7", what, e.first));
+        e.second.validate(g_.dec.H, g_.dec.W);
+    }
+}
+
+Engine::MatchResult Engine::match(const std::vector<std::pair<int, MatchTemplate>>& ts, i64 max_hits, bool positions) {
+    check_match(ts, "match()");
+    if (max_hits < 1) throw Error(strprintf("match(): max_hits = %lld is less than 1", (long long)max_hits));
+    MatchResult res;
+    std::vector<i32> pos;
+    std::vector<u8> ids;
+    for (const auto& e : ts) {  // one bitmap, reused: match, read the count, compact, then the next orientation
+        const u64 n = match_local(e.second, positions, false);
+        stats_.match_launches += 1;
+        res.count += n;
+        const i64 room = max_hits - (i64)ids.size();
+        if (!positions || n == 0 || room <= 0) continue;
+        const i64 take = (i64)std::min<u64>(n, (u64)room);
+        match_positions_local(take, &pos);
+        ids.resize(ids.size() + (size_t)take, (u8)e.first);
+    }
+    res.truncated = res.count > (u64)max_hits;
+    if (!positions) return res;
+    std::vector<size_t> order(ids.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+        if (pos[2 * a] != pos[2 * b]) return pos[2 * a] < pos[2 * b];
+        if (pos[2 * a + 1] != pos[2 * b + 1]) return pos[2 * a + 1] < pos[2 * b + 1];
+        return ids[a] < ids[b];
+    });
+    res.positions.reserve(pos.size());
+    res.orientation.reserve(ids.size());
+    for (size_t i : order) {
+        res.positions.push_back(pos[2 * i]);
+        res.positions.push_back(pos[2 * i + 1]);
+        res.orientation.push_back(ids[i]);
+    }
+    return res;
+}
+
+void Engine::match_cells(const std::vector<std::pair<int, MatchTemplate>>& ts, const CellBuffer& dst) {
+    check_match(ts, "match_cells()");
+    need_cells(dst, L_.h * L_.w, "match_cells()");
+    check_cell_pointer(dst, "match_cells()");
+    for (size_t i = 0; i < ts.size(); ++i) {
+        match_local(ts[i].second, true, i > 0);
+        stats_.match_launches += 1;
+    }
+    match_bitmap_cells(dst);
+}
+
+// ---------------------------------------------------------------------------------------------
 // CPU backend
 // ---------------------------------------------------------------------------------------------
 
@@ -990,6 +1051,29 @@ class CpuEngine : public Engine {
         t.row_stride = L_.pitch, t.rows = L_.h, t.cols = L_.w;
         pack_cells_host(src, t);
         refresh_local(cur_);
+    }
+    // pattern matching: the host matcher on the board's natural-order words; the bitmap stays in natural order
+    u64 match_local(const MatchTemplate& t, bool keep, bool or_into) override {
+        std::vector<u64> d((size_t)(L_.h * L_.nw));
+        cpu::extract_words(cur_, L_, d.data());
+        if (keep) match_bits_.resize(d.size(), 0);
+        return match_host(d.data(), L_.h, L_.w, !dead_edges(), t, keep ? match_bits_.data() : nullptr, or_into);
+    }
+    void match_positions_local(i64 cap, std::vector<i32>* out) override {
+        match_positions_host(match_bits_.data(), L_.h, L_.w, cap, out);
+    }
+    void match_bitmap_cells(const CellBuffer& dst) override {
+        std::vector<u64> split(match_bits_.size());
+        for (size_t i = 0; i < split.size(); ++i) split[i] = split_word(match_bits_[i]);
+        CellSource s;
+        s.base = split.data();
+        s.words = (i64)split.size();
+        s.frame_stride = 0, s.row_stride = L_.nw;
+        s.n = 1, s.rows = L_.h, s.cols = L_.w;
+        s.r0 = 0, s.H = L_.h;
+        s.c0 = 0, s.W = L_.w;
+        s.w0 = 0, s.gwords = L_.nw, s.fw = L_.nw;
+        unpack_cells_host(s, dst);
     }
     size_t film_chunk() const override {  // (the host record between two drains stays below 64 MiB)
         return std::max<size_t>(8, ((size_t)64 << 20) / ((size_t)film_geo_.slot_words() * sizeof(u64)));
@@ -1098,6 +1182,7 @@ class CpuEngine : public Engine {
     const u64* view_buf() const { return view_env_ ? env_.data() : cur_; }
     std::vector<u64> a_, b_, snap_;
     std::vector<u64> env_;  // envelope mode: E in the board's layout
+    std::vector<u64> match_bits_;  // match(): the last bitmap, h x nw natural-order words
     u64* cur_;
     u64* oth_;
     std::vector<std::vector<u64>> stage_s_, stage_r_;

@@ -261,7 +261,8 @@ HipEngine::~HipEngine() {
     for (void* q : {(void*)res_status_, (void*)res_scratch_[0], (void*)res_scratch_[1]})
         if (q) hipFree(q);
     for (void* p : deferred_free_) hipFree(p);
-    for (void* p : {(void*)d_view_, (void*)d_grid_, (void*)d_pat_, (void*)d_census_, (void*)d_snap_, (void*)d_env_})
+    for (void* p : {(void*)d_view_, (void*)d_grid_, (void*)d_pat_, (void*)d_census_, (void*)d_snap_, (void*)d_env_,
+                    (void*)d_match_, (void*)d_match_cnt_, (void*)d_match_pos_})
         if (p) hipFree(p);
     if (h_view_) hipHostFree(h_view_);
     hipFree(d_red_);

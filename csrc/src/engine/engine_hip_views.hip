@@ -3,6 +3,7 @@
 // Readers first bring the canonical board up to date and drain the engine's streams, as tile_words() does;
 // the stamp then refreshes ghosts and events exactly as set_tile_words() does.  Staging buffers grow on demand
 // and are reused; an outgrown one is freed with the engine (hipFree may synchronise the whole device).
+#include "../hip/tensor_kernels.hpp"
 #include "hip_engine.hpp"
 
 namespace gol {
@@ -75,6 +76,45 @@ void HipEngine::density_local(i64 block_rows, i64 block_cols, u32* counts) {
     HIP_CHECK(hipMemcpyAsync(host, d_grid_, bytes, hipMemcpyDeviceToHost, s_comp_));  // only the grid leaves the device
     HIP_CHECK(hipStreamSynchronize(s_comp_));
     for (i64 i = 0; i < grows * gcols; ++i) counts[i] += host[i];
+}
+
+// One k_match launch over the canonical board.  The bitmap (keep) is a buffer in the board's layout, of which the
+// kernel writes words 0 .. nw - 1 of rows 0 .. h - 1; only the counter comes to the host.
+u64 HipEngine::match_local(const MatchTemplate& t, bool keep, bool or_into) {
+    sync_canonical();
+    synchronize();
+    check_res_status();
+    if (keep) grow_device((void**)&d_match_, &d_match_cap_, (size_t)L_.bytes());
+    grow_device((void**)&d_match_cnt_, &d_match_cnt_cap_, 2 * sizeof(u64));
+    u64* host = reinterpret_cast<u64*>(view_host(2 * sizeof(u64)));
+    HIP_CHECK(hipMemsetAsync(d_match_cnt_, 0, 2 * sizeof(u64), s_comp_));
+    hipk::launch_match(buf_[cur_], hipk::match_geo(L_, !dead_edges()), t, keep ? d_match_ : nullptr, or_into, nullptr,
+                       d_match_cnt_, s_comp_);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(host, d_match_cnt_, sizeof(u64), hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    return host[0];
+}
+
+void HipEngine::match_positions_local(i64 cap, std::vector<i32>* out) {
+    if (cap < 1) return;
+    if (!d_match_) throw Error("match: no bitmap to compact");
+    const size_t bytes = (size_t)cap * 2 * sizeof(i32);
+    grow_device((void**)&d_match_pos_, &d_match_pos_cap_, bytes);
+    i32* host = reinterpret_cast<i32*>(view_host(bytes));
+    HIP_CHECK(hipMemsetAsync(d_match_cnt_ + 1, 0, sizeof(u64), s_comp_));
+    hipk::launch_match_positions(d_match_, hipk::match_geo(L_, !dead_edges()), d_match_pos_, cap, d_match_cnt_ + 1, s_comp_);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(host, d_match_pos_, bytes, hipMemcpyDeviceToHost, s_comp_));  // only the positions leave the device
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    out->insert(out->end(), host, host + 2 * cap);
+}
+
+void HipEngine::match_bitmap_cells(const CellBuffer& dst) {
+    if (!d_match_) throw Error("match: no bitmap to unpack");
+    hipk::launch_cells_from_words(tile_source(d_match_, 0, 0, L_.h, L_.w), dst, s_comp_);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
 }
 
 void HipEngine::stamp_local(const RlePattern& p, i64 r0, i64 c0, StampMode mode) {

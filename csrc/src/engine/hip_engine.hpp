@@ -117,6 +117,10 @@ class HipEngine : public Engine {
     void read_window_local(i64 r0, i64 c0, i64 rows, i64 cols, u8* out, i64 stride) override;
     void density_local(i64 block_rows, i64 block_cols, u32* counts) override;
     void stamp_local(const RlePattern& p, i64 r0, i64 c0, StampMode mode) override;
+    // pattern matching (engine_hip_views.hip; kernels: src/hip/match_kernel.hip)
+    u64 match_local(const MatchTemplate& t, bool keep, bool or_into) override;
+    void match_positions_local(i64 cap, std::vector<i32>* out) override;
+    void match_bitmap_cells(const CellBuffer& dst) override;
 
     // dense cells on the device (engine_hip_cells.hip; kernels: src/hip/tensor_kernels.hip)
     void check_cell_pointer(const CellBuffer& b, const char* what) override;
@@ -722,6 +726,12 @@ class HipEngine : public Engine {
     u64* d_pat_ = nullptr;
     u8* h_view_ = nullptr;
     size_t d_view_cap_ = 0, d_grid_cap_ = 0, d_pat_cap_ = 0, h_view_cap_ = 0;
+    // match(): the bitmap in the board's layout (board-sized, allocated on first use), the counter and the cursor
+    // (two u64), and the compacted positions
+    u64* d_match_ = nullptr;
+    u64* d_match_cnt_ = nullptr;
+    i32* d_match_pos_ = nullptr;
+    size_t d_match_cap_ = 0, d_match_cnt_cap_ = 0, d_match_pos_cap_ = 0;
     std::map<i64, DevPlan> plans_;
     // GOL_SUBTILES=2 state
     bool dual_ = false;

@@ -104,6 +104,23 @@ class HipSoups final : public SoupBatch {
         hipk::launch_reset_soup_states(state_, (u32)cfg_.n, stream_);
         reset();
     }
+    // k_match (src/hip/match_kernel.hip) over the store: n dense tori of S rows x m words, one counter per soup
+    void do_match_counts(const std::vector<MatchTemplate>& oriented, u32* counts) override {
+        use();
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        if (!match_counts_) HIP_CHECK(hipMalloc(&match_counts_, (size_t)cfg_.n * sizeof(u32)));
+        hipk::MatchGeo g;
+        g.base = 0, g.pitch = m(), g.batch_stride = wps_;
+        g.w = cfg_.size, g.h = (i32)cfg_.size, g.nw = m();
+        g.torus = 1, g.batch = (i32)cfg_.n;
+        HIP_CHECK(hipMemsetAsync(match_counts_, 0, (size_t)cfg_.n * sizeof(u32), stream_));
+        for (const MatchTemplate& t : oriented) {
+            hipk::launch_match(board_, g, t, nullptr, false, match_counts_, nullptr, stream_);
+            HIP_CHECK(hipGetLastError());
+        }
+        HIP_CHECK(hipMemcpyAsync(counts, match_counts_, (size_t)cfg_.n * sizeof(u32), hipMemcpyDeviceToHost, stream_));
+        HIP_CHECK(hipStreamSynchronize(stream_));
+    }
 
    private:
     size_t bytes() const { return (size_t)cfg_.n * (size_t)wps_ * sizeof(u64); }
@@ -134,8 +151,9 @@ class HipSoups final : public SoupBatch {
         return v;
     }
     void release() {
-        for (void* p : {(void*)board_, (void*)saved_, (void*)init_, (void*)tmp_, (void*)state_, (void*)counters_})
+        for (void* p : {(void*)board_, (void*)saved_, (void*)init_, (void*)tmp_, (void*)state_, (void*)counters_, (void*)match_counts_})
             if (p) (void)hipFree(p);
+        match_counts_ = nullptr;
         board_ = saved_ = init_ = tmp_ = nullptr;
         state_ = nullptr;
         counters_ = nullptr;
@@ -148,6 +166,7 @@ class HipSoups final : public SoupBatch {
     u64 *board_ = nullptr, *saved_ = nullptr, *init_ = nullptr, *tmp_ = nullptr;
     SoupState* state_ = nullptr;
     u32* counters_ = nullptr;
+    u32* match_counts_ = nullptr;  // match_counts(): one counter per soup, allocated on first use
 };
 
 }  // namespace

@@ -702,6 +702,55 @@ class Simulation:
         self.engine.stamp(p, int(at[0]), int(at[1]), mode)
         return self
 
+    # -- pattern matching (ops/match.py states what a template is and when it matches) -----------
+    def _match_templates(self, what: str, pattern_or_template, margin: int, orientations):
+        """The native ``[(orientation id, template)]`` of a call; every refusal is a ValueError, before any launch."""
+        from ..ops.match import as_template, want_all
+
+        self._one_rank(what)
+        all_ = want_all(orientations)
+        t = as_template(pattern_or_template, margin)
+        H, W = self.decomposition.H, self.decomposition.W
+        ts = t.native.orientations(all_)
+        for _, o in ts:
+            if o.th > H or o.tw > W:
+                raise ValueError(f"{what}: the template is {o.th} x {o.tw} cells, the board {H} x {W}")
+        return ts
+
+    def match(self, pattern_or_template, *, margin: int = 1, orientations=False, max_hits: int = 1 << 20,
+              positions: bool = True):
+        """Where a pattern sits on the current board: :class:`ops.MatchResult` ``(count, positions, orientation,
+        truncated)``.  ``pattern_or_template``: what :meth:`stamp` accepts, turned into a template with ``margin`` dead
+        cells around it (``ops.match_template``), or an ``ops.Template``.  ``orientations``: ``False`` (as given) or
+        ``"all"`` (the distinct ones of the eight turns and mirror images).  ``positions`` is a ``(k, 2)`` int64 array of
+        the board cells under the pattern's top-left cell, sorted by (row, col, orientation), ``orientation`` their ids.
+        ``count`` is always exact; with ``count > max_hits``, ``truncated`` is True and the positions are some ``max_hits``
+        of the matches.  ``positions=False`` returns the count alone (empty arrays).  One rank only.  On the HIP backend
+        the board stays on the device: only the counter and the positions leave it."""
+        ts = self._match_templates("match", pattern_or_template, margin, orientations)
+        max_hits = int(max_hits)
+        if max_hits < 1:
+            raise ValueError(f"match: max_hits = {max_hits} is less than 1")
+        from ..ops.match import MatchResult
+
+        count, pos, ids, truncated = self.engine.match(ts, max_hits, bool(positions))
+        return MatchResult(int(count), pos, ids, bool(truncated))
+
+    def count_matches(self, pattern_or_template, *, margin: int = 1, orientations=False) -> int:
+        """``match(...).count`` with nothing but the counter leaving the device."""
+        return self.match(pattern_or_template, margin=margin, orientations=orientations, positions=False).count
+
+    def match_tensor(self, pattern_or_template, *, margin: int = 1, orientations=False, dtype=None, out=None):
+        """The matches as an ``(h, w)`` tensor on the simulation's side: 1 where some requested orientation matches, else
+        0.  Arguments as :meth:`match`; dtype, ``out``, stream ordering and errors as :meth:`board_tensor`."""
+        from ..ops import tensors
+
+        ts = self._match_templates("match_tensor", pattern_or_template, margin, orientations)
+        t = tensors.result((self.geometry.h, self.geometry.w), dtype, self._tensor_device(), out, "match_tensor")
+        tensors.sync(t)
+        self.engine.match_cells(ts, *tensors.handle(t))
+        return t
+
     def load_rle(self, path, at="center") -> "Simulation":
         """An empty board (generation 0) with the file's pattern on it.  Raises if the file names a rule
         other than the simulation's."""

@@ -136,6 +136,21 @@ class SoupBatch:
         idx = list(range(self.n)) if indices is None else [int(i) for i in indices]
         return self._native.boards(idx)
 
+    def match_counts(self, patterns, margin: int = 1, orientations="all") -> np.ndarray:
+        """An ``(n, len(patterns))`` uint32 array: entry ``(i, t)`` is the number of matches of ``patterns[t]`` (what
+        ``Simulation.match`` accepts: a pattern, isolated by ``margin`` dead cells, or an ``ops.Template``), summed over
+        its requested orientations, on soup ``i``'s current board (a torus).  HIP: one ``k_match`` launch per oriented
+        template over all soups; only the counts leave the device.  A pending :meth:`step` is included."""
+        from ..ops.match import as_template, want_all
+
+        all_ = want_all(orientations)
+        templates = [[o for _, o in as_template(p, margin).native.orientations(all_)] for p in patterns]
+        for ts in templates:
+            for o in ts:
+                if o.th > self.size or o.tw > self.size:
+                    raise ValueError(f"soups: match_counts: the template is {o.th} x {o.tw} cells, a soup {self.size} x {self.size}")
+        return self._native.match_counts(templates)
+
     def stats(self) -> dict:
         """``kernel`` (``soups@64``, ``soups@128``, ``soups@256``; ``:rule`` appended for the generic variant), ``launches``,
         ``settled``, ``reached`` (the generation of the unsettled soups), ``backend``, ``rule``, ``workgroup``."""
