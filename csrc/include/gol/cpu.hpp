@@ -66,7 +66,13 @@ struct DensityOut {
 };
 u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule = Rule(), const Edges& edges = Edges(),
                u64* counts = nullptr, u64* sigs = nullptr, const FilmOut& film = FilmOut(),
-               const DensityOut& density = DensityOut(), u64* envelope = nullptr);
+               const DensityOut& density = DensityOut(), u64* envelope = nullptr, i64 plane_stride = 0);
+// Generations rules (rule.states > 2, gol/rule.hpp): a and b hold 1 + M planes in layout L, plane_stride >= L.words()
+// words apart: plane 0 the live cells (state 1), planes 1 .. M the bits of the decay counter d = state - 1 of the dying
+// cells, M = rule.decay_planes().  Every plane is masked, stepped and extended like the live plane (the decay counter of a
+// ghost row is needed: a dying cell there cannot be born); no cell is alive and dying.  counts, sigs, film, density and
+// envelope must be off.  state_counts: counts[s] += the tile's own cells in state s, s = 0 .. rule.states - 1.
+void state_counts(const u64* buf, const Layout& L, i64 plane_stride, const Rule& rule, u64* counts);
 // envelope (envelope mode; nullptr: none): a buffer in layout L; after every generation the tile's own cells (rows
 // [0, h), words [0, nw), storage mask on the last word) are ORed into it.  envelope_or does that for one board.
 void envelope_or(u64* envelope, const u64* board, const Layout& L);

@@ -126,8 +126,9 @@ struct EngineStats {
     int predicted_gens = 0;     // generations of the timed supersteps behind it
     double t_exchange_ms = 0;  // profile only
     double t_compute_ms = 0;   // profile only
-    std::string kernel;        // stencil kernel in use (HIP: temporal | tile | lds | rule@K; CPU: cpu)
-    std::string rule;          // the rule, canonical (B3/S23)
+    std::string kernel;        // stencil kernel in use (HIP: temporal | tile | lds | rule@K | gen@K; CPU: cpu)
+    std::string rule;          // the rule, canonical (B3/S23; a Generations rule: B2/S345/C4)
+    int states = 2;            // its states: 2, or C of a Generations rule
     std::string boundary;      // torus | dead
     bool census = false;       // census mode
     bool signature = false;    // signature mode
@@ -198,6 +199,23 @@ class Engine {
     u64 snapshot_diff();
     // run() keeps a record made inside the stepping kernel: per generation, or (envelope mode) one OR over them
     bool recording() const { return cfg_.census || cfg_.signature || cfg_.film.on || cfg_.density_film.on || cfg_.envelope; }
+
+    // ----- Generations rules (EngineConfig::rule with states > 2; gol/rule.hpp) -----
+    // The board is 1 + M planes in one layout: the live plane (state 1), which is the board every other call of this
+    // class reads and writes (tile_words, population, density, fingerprint, signature, snapshot*, match, window, stamp),
+    // and the M planes of the decay counter of the dying cells.  No cell is alive and dying; tail bits, ghost words
+    // outside a bounded board and slack rows are zero in every plane.  One rank only.  init() and set_tile_words() zero
+    // the decay planes; stamp() acts on the live plane and then clears the decay counter of every live cell (so a
+    // stamped cell is alive, and `replace` and `clear` leave dying cells dying).  HIP: step_gen runs every pass.
+    // The calls below throw on an engine whose rule has two states.
+    int states() const { return (int)cfg_.rule.states; }
+    bool generations() const { return cfg_.rule.generations(); }
+    std::vector<u8> state_tile();                          // h x w bytes: the state 0 .. C-1 of every cell of the tile
+    void set_state_tile(const std::vector<u8>& states);    // (every value checked to be < C before anything is written)
+    std::vector<u8> state_window(i64 r0, i64 c0, i64 rows, i64 cols);  // window()'s coordinates and checks
+    std::vector<u64> state_counts();                       // C counts: the cells of the board in each state
+    // Throws, naming the call and the rule, under a Generations rule: what is not built for them in this version.
+    void need_two_states(const char* what) const;
 
     // ----- envelope (EngineConfig::envelope) -----
     // E = board(start) | board(start + 1) | ... | board(generation()), cell by cell, with start the generation of the
@@ -451,6 +469,16 @@ class Engine {
     void need_envelope(const char* what) const;
     bool view_env_ = false;
     u64 env_start_ = 0;
+    // Generations rules.  view_plane_: the plane tile_words(), read_window_local(), density_local() and local_reduce()
+    // read (0: the live plane; set for the length of a state reader).  write_planes_local: the tile's 1 + M planes from
+    // dense natural-order words (h * nw each; a null entry: zeros), then what set_tile_words() does after its copy.
+    // settle_decay_local: every decay plane ANDed with the complement of the live plane over the tile, ghosts refreshed.
+    // state_counts_local: counts[s] += this rank's cells in state s.
+    int view_plane_ = 0;
+    virtual void write_planes_local(const std::vector<const u64*>& planes) = 0;
+    virtual void settle_decay_local() = 0;
+    virtual void state_counts_local(u64* counts) = 0;
+    void need_generations(const char* what) const;
     // Dense cells: the backends' parts.  check_cell_pointer: throw unless the buffer's memory is the backend's kind
     // (HIP: device memory of the engine's device; CPU: nothing to ask).  read_rect_cells: the rectangle of the board
     // (view_env_: the envelope) in tile coordinates, wrapping at the tile's edges.  write_tile_cells_local: the cells

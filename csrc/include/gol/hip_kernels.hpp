@@ -20,6 +20,9 @@
 //   wave with that neighbourhood's gates (nbhd_gates.hpp; instantiated in nbhd_rule_kernel.hip, nbhd_bounded_kernel.hip,
 //   nbhd_census_kernel.hip, nbhd_signature_kernel.hip; K = 1..8): the depth and occupancy queries below take the
 //   neighbourhood for that reason.
+//   step_gen<K, M>    — Generations rules (B/S/C): step_rule / step_rule_bounded on the live plane with the dying
+//                       cells' decay counter, M more bit planes, carried through the levels (generations_kernel.hip;
+//                       K = 1 .. max_generations_depth(C); with k_state_counts and k_settle_decay in aux_kernels.hip).
 //   step_soups<M>     — soup batches (gol/soups.hpp), beside the engine: many independent 64 M x 64 M tori per launch, one
 //                       wave64 per soup with the board in registers, settled inside the kernel (soup_kernel.hip; its host
 //                       API is src/hip/soup_kernel.hpp).
@@ -180,6 +183,23 @@ int max_envelope_depth(Nbhd nbhd = Nbhd::Moore);
 int envelope_blocks_per_cu(int k, u32 flags, bool bounded, Nbhd nbhd = Nbhd::Moore);
 void launch_step_envelope(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src, u64* dst,
                           u64* env, const LaneDesc* plan, i64 n_waves, const StepParams& p, hipStream_t s);
+// step_gen<K, M> (generations_kernel.hip): K generations of a Generations rule (rule.states = C in 3 .. 9, Moore).  src
+// and dst are boards of 1 + M planes in one layout, plane_stride words apart, M = rule.decay_planes(): plane 0 the live
+// cells, which the kernel steps as step_rule / step_rule_bounded step a board, planes 1 .. M the decay counter of the
+// dying cells.  In every plane it writes exactly the rows and words launch_step_rule writes in a board for the same plan,
+// and reads the ones it reads, or at most three rows past a segment's last input row (within the slack rows the
+// runner's prefetch requires); board_words is what the caller allocated per plane (the board, its halo and slack rows),
+// and a plane_stride below it is refused.  `place`, `bounded`, tile_cols and the other argument checks as
+// launch_step_envelope.  Depths 1 .. max_generations_depth(C).
+int max_generations_depth(int states);
+int generations_blocks_per_cu(int k, u32 flags, bool bounded, int states);
+void launch_step_gen(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src, u64* dst,
+                     i64 plane_stride, i64 board_words, const LaneDesc* plan, i64 n_waves, const StepParams& p, hipStream_t s);
+// Generations rules (aux_kernels.hip).  state_counts: the tile's own cells in state s, s = 0 .. C - 1, added to the kCensusStripes
+// partial sums of slot s of `out` (the census's layout: C slots of kCensusSlotWords words, zeroed by the caller).
+// settle_decay: every decay plane ANDed with the complement of the live plane over the tile's own words.
+void launch_state_counts(const u64* buf, const Layout& L, i64 plane_stride, const Rule& rule, u64* out, hipStream_t s);
+void launch_settle_decay(u64* buf, const Layout& L, i64 plane_stride, const Rule& rule, hipStream_t s);
 // env = (reset ? 0 : env) | the tile's own cells of `board` (aux_kernels.hip; both buffers in layout L).
 void launch_envelope_merge(u64* env, const u64* board, const Layout& L, bool reset, hipStream_t s);
 // out[0] += the signature of the tile in `buf` at (grow0, gword0) (wrapping; out zeroed by the caller).

@@ -121,6 +121,7 @@ py::dict stats_dict(const EngineStats& s) {
     d["t_compute_ms"] = s.t_compute_ms;
     d["kernel"] = s.kernel;
     d["rule"] = s.rule;
+    d["states"] = s.states;
     d["boundary"] = s.boundary;
     d["census"] = s.census;
     d["signature"] = s.signature;
@@ -393,6 +394,14 @@ PYBIND11_MODULE(_gol, m) {
             throw py::value_error(e.what());
         }
     });
+    // rule string -> its states: 2 for a life-like rule, C of a Generations rule B<digits>/S<digits>/C<n>
+    m.def("parse_rule_states", [](const std::string& s) {
+        try {
+            return (int)Rule::parse(s).states;
+        } catch (const Error& e) {
+            throw py::value_error(e.what());
+        }
+    });
 
     py::class_<Engine>(m, "Engine")
         .def_static(
@@ -532,6 +541,60 @@ PYBIND11_MODULE(_gol, m) {
         .def("signature", &Engine::signature, py::call_guard<py::gil_scoped_release>())
         .def("snapshot", &Engine::snapshot, py::call_guard<py::gil_scoped_release>())
         .def("snapshot_diff", &Engine::snapshot_diff, py::call_guard<py::gil_scoped_release>())
+        // Generations rules: the states of the tile (h, w) uint8, the reverse, the states of a window, the C counts;
+        // what a call refuses (a two-state rule, a value >= C) is a ValueError
+        .def_property_readonly("states", &Engine::states)
+        .def("state_tile",
+             [](Engine& e) {
+                 std::vector<u8> v;
+                 try {
+                     py::gil_scoped_release r;
+                     v = e.state_tile();
+                 } catch (const Error& err) {
+                     throw py::value_error(err.what());
+                 }
+                 py::array_t<u8> a({(py::ssize_t)e.layout().h, (py::ssize_t)e.layout().w});
+                 std::memcpy(a.mutable_data(), v.data(), v.size());
+                 return a;
+             })
+        .def("set_state_tile",
+             [](Engine& e, py::array_t<u8, py::array::c_style | py::array::forcecast> a) {
+                 std::vector<u8> v(a.data(), a.data() + a.size());
+                 try {
+                     py::gil_scoped_release r;
+                     e.set_state_tile(v);
+                 } catch (const Error& err) {
+                     throw py::value_error(err.what());
+                 }
+             })
+        .def(
+            "state_window",
+            [](Engine& e, i64 r0, i64 c0, i64 rows, i64 cols) {
+                std::vector<u8> v;
+                try {
+                    py::gil_scoped_release r;
+                    v = e.state_window(r0, c0, rows, cols);
+                } catch (const Error& err) {
+                    throw py::value_error(err.what());
+                }
+                py::array_t<u8> a({(py::ssize_t)rows, (py::ssize_t)cols});
+                std::memcpy(a.mutable_data(), v.data(), v.size());
+                return a;
+            },
+            py::arg("r0"), py::arg("c0"), py::arg("rows"), py::arg("cols"))
+        .def("state_counts",
+             [](Engine& e) {
+                 std::vector<u64> v;
+                 try {
+                     py::gil_scoped_release r;
+                     v = e.state_counts();
+                 } catch (const Error& err) {
+                     throw py::value_error(err.what());
+                 }
+                 py::array_t<u64> a((py::ssize_t)v.size());
+                 std::memcpy(a.mutable_data(), v.data(), v.size() * sizeof(u64));
+                 return a;
+             })
         // views and stamping (collective; global board coordinates on the torus)
         .def(
             "window",
@@ -930,6 +993,14 @@ PYBIND11_MODULE(_gol, m) {
     m.def("max_film_depth", []() { return hipk::max_film_depth(); });            // ... of the film kernel
     m.def("max_envelope_depth", []() { return hipk::max_envelope_depth(); });    // ... of the envelope kernel
     m.def("max_density_depth", []() { return hipk::max_density_depth(); });      // ... of the density kernel
+    // ... of the Generations kernel step_gen for a rule of `states` states (3 .. 9); ValueError on anything else
+    m.def("max_generations_depth", [](int states) {
+        try {
+            return hipk::max_generations_depth(states);
+        } catch (const Error& e) {
+            throw py::value_error(e.what());
+        }
+    }, py::arg("states"));
     m.attr("density_film_max_blocks") = kDensityFilmMaxBlocks;                   // blocks of the finest grid density-film mode takes
     m.attr("film_max_cells") = kFilmMaxCells;                                    // cells of the largest window film mode takes
     m.def(

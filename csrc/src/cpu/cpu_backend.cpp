@@ -211,9 +211,89 @@ void envelope_or(u64* envelope, const u64* board, const Layout& L) {
     }
 }
 
+namespace {
+
+// One generation of a Generations rule for rows [r_lo, r_hi) (words -1 .. nw): the live plane of dst holds R, the
+// two-state step of the source's live plane; A is the source's live plane and d its decay counter (planes 1 .. M).
+//   A' = R & ~any(d)                                             a dying cell is not born
+//   d' = (A & ~R) ? 1 : (any(d) & d != C - 2 ? d + 1 : 0)          a cell that fails to survive starts to decay
+void gen_rows(const u64* src, u64* dst, const Layout& L, i64 plane_stride, i64 r_lo, i64 r_hi, const Rule& rule) {
+    const int M = rule.decay_planes();
+    const unsigned last = (unsigned)rule.states - 2u;
+    const i64 n = L.nw + 2;
+#pragma omp parallel for schedule(static) if ((r_hi - r_lo) * n > 16384)
+    for (i64 r = r_lo; r < r_hi; ++r) {
+        const i64 at = L.index(r, -1);
+        for (i64 j = 0; j < n; ++j) {
+            const u64 A = src[at + j], R = dst[at + j];
+            u64 d[3] = {0, 0, 0}, any = 0, eq = ~0ull;
+            for (int m = 0; m < M; ++m) {
+                d[m] = src[(m + 1) * plane_stride + at + j];
+                any |= d[m];
+                eq &= (last >> m) & 1u ? d[m] : ~d[m];
+            }
+            const u64 start = A & ~R, keep = any & ~eq;
+            dst[at + j] = R & ~any;
+            u64 carry = ~0ull;  // d + 1: a ripple over the planes
+            for (int m = 0; m < M; ++m) {
+                const u64 sum = d[m] ^ carry;
+                carry &= d[m];
+                dst[(m + 1) * plane_stride + at + j] = (keep & sum) | (m == 0 ? start : 0);
+            }
+        }
+    }
+}
+
+u64* superstep_generations(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges, i64 plane_stride) {
+    if (plane_stride < L.words())
+        throw Error(strprintf("superstep: a plane stride of %lld words is less than a board of %lld", (long long)plane_stride,
+                              (long long)L.words()));
+    Rule two = rule;  // the births and survivals: the life-like rule with the same masks
+    two.states = 2;
+    const int M = rule.decay_planes();
+    u64* src = a;
+    u64* dst = b;
+    for (int m = 0; m <= M; ++m) mask_rows(src + m * plane_stride, L, -(i64)k, L.h + k, edges);
+    for (int g = 0; g < k; ++g) {
+        const i64 ext = k - 1 - g;
+        step_rows(src, dst, L, -ext, L.h + ext, two, edges);
+        gen_rows(src, dst, L, plane_stride, -ext, L.h + ext, rule);
+        std::swap(src, dst);
+    }
+    return src;
+}
+
+}  // namespace
+
+void state_counts(const u64* buf, const Layout& L, i64 plane_stride, const Rule& rule, u64* counts) {
+    const int M = rule.decay_planes();
+    for (i64 r = 0; r < L.h; ++r)
+        for (i64 c = 0; c < L.nw; ++c) {
+            const i64 at = L.index(r, c);
+            const u64 own = storage_mask(c, L.w), A = buf[at] & own;
+            u64 any = 0;
+            for (int m = 0; m < M; ++m) any |= buf[(m + 1) * plane_stride + at];
+            counts[0] += (u64)__builtin_popcountll(own & ~A & ~any);
+            counts[1] += (u64)__builtin_popcountll(A);
+            for (int s = 2; s < (int)rule.states; ++s) {
+                u64 is = own;  // d == s - 1
+                for (int m = 0; m < M; ++m) {
+                    const u64 p = buf[(m + 1) * plane_stride + at];
+                    is &= ((s - 1) >> m) & 1 ? p : ~p;
+                }
+                counts[s] += (u64)__builtin_popcountll(is);
+            }
+        }
+}
+
 u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges, u64* counts, u64* sigs,
-               const FilmOut& film, const DensityOut& density, u64* envelope) {
+               const FilmOut& film, const DensityOut& density, u64* envelope, i64 plane_stride) {
     if (k < 1 || k > L.R) throw Error(strprintf("superstep depth %d outside 1..%d", k, L.R));
+    if (rule.generations()) {
+        if (counts || sigs || film.frames || density.maps || envelope)
+            throw Error("superstep: the per-generation records and the envelope are not built for Generations rules (" + rule.str() + ")");
+        return superstep_generations(a, b, L, k, rule, edges, plane_stride);
+    }
     u64* src = a;
     u64* dst = b;
     mask_rows(src, L, -(i64)k, L.h + k, edges);

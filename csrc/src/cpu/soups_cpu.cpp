@@ -17,6 +17,8 @@ void SoupBatch::validate(const SoupConfig& c) {
                               (long long)c.size));
     if (c.n < 1 || c.n > kSoupsMax)
         throw Error(strprintf("soups: n = %lld is outside 1 .. 2^20", (long long)c.n));
+    if (c.rule.generations())
+        throw Error("soups: rule " + c.rule.str() + " is a Generations rule; soup batches run two-state rules only in this version");
     if (c.rule.nbhd != Nbhd::Moore)
         throw Error("soups: rule " + c.rule.str() + " counts the " + nbhd_name(c.rule.nbhd) +
                     " neighbourhood; soup batches run Moore rules only");

@@ -22,7 +22,28 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     : g_(g), cfg_(c), t_(std::move(t)) {
     if (!t_) throw Error("engine needs a transport");
     xchg_self_ = cfg_.self_exchange && !cfg_.compat;
-    Rule::from_masks(cfg_.rule.birth, cfg_.rule.survive, cfg_.rule.nbhd);  // (a rule set by its masks: range and B0 checks)
+    Rule::from_masks(cfg_.rule.birth, cfg_.rule.survive, cfg_.rule.nbhd, cfg_.rule.states);  // (a rule set by its masks: range and B0 checks)
+    if (cfg_.rule.generations()) {
+        // A Generations rule is a mode of its own: one rank, no in-kernel record, the generic streaming pass only.
+        const std::string rs = cfg_.rule.str();
+        auto refuse = [&rs](const char* option, const char* why) {
+            throw Error(std::string(option) + " with the Generations rule " + rs + ": " + why);
+        };
+        if (g_.dec.P > 1)
+            throw Error(strprintf("the Generations rule %s on %d ranks: Generations rules run on one rank (the exchange of the "
+                                  "decay planes is not built)", rs.c_str(), g_.dec.P));
+        if (cfg_.census) refuse("census", "the census kernel counts two-state boards");
+        if (cfg_.signature) refuse("signature", "the signature kernel hashes two-state boards");
+        if (cfg_.film.on) refuse("film", "the film kernel stores two-state frames");
+        if (cfg_.density_film.on) refuse("density_film", "the density kernel counts two-state boards");
+        if (cfg_.envelope) refuse("envelope", "the envelope kernel records two-state boards");
+        if (cfg_.compat) refuse("compat (GOL_COMPAT=reference)", "the reference has one rule, B3/S23");
+        if (cfg_.subtiles == 2) refuse("subtiles=2 (GOL_SUBTILES=2)", "the sub-tile halves run B3/S23 only");
+        if (cfg_.self_exchange) refuse("self_exchange (GOL_SELF_EXCHANGE)", "the exchange of the decay planes is not built");
+        if (cfg_.force_split) refuse("force_split (GOL_FORCE_SPLIT)", "the split schedule's exchange of the decay planes is not built");
+        if (cfg_.backend == "hip" && cfg_.kernel != "auto" && cfg_.kernel != "rule")
+            refuse(("kernel '" + cfg_.kernel + "'").c_str(), "step_gen runs every pass (use kernel auto or rule)");
+    }
     if (!cfg_.rule.is_conway()) {
         const std::string rs = cfg_.rule.str();
         if (cfg_.compat) throw Error("GOL_COMPAT=reference with rule " + rs + ": the reference has one rule, B3/S23");
@@ -153,6 +174,7 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     L_ = Layout(g_.h, g_.w, R);
     stats_.depth = R;
     stats_.rule = cfg_.rule.str();
+    stats_.states = (int)cfg_.rule.states;
     stats_.boundary = boundary_name(cfg_.boundary);
     stats_.census = cfg_.census;
     stats_.signature = cfg_.signature;
@@ -258,6 +280,7 @@ void Engine::init(const PatternSpec& p) {
     stats_.schedule = halo_items(L_.R).empty() ? "local" : "full";
     stats_.kernel_depth = L_.R;
     stats_.rule = cfg_.rule.str();
+    stats_.states = (int)cfg_.rule.states;
     stats_.boundary = boundary_name(cfg_.boundary);
     stats_.census = cfg_.census;
     stats_.signature = cfg_.signature;
@@ -604,6 +627,92 @@ void Engine::envelope_clear() {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Generations rules (the backends keep 1 + M planes; the board's readers run on each plane)
+// ---------------------------------------------------------------------------------------------
+
+void Engine::need_generations(const char* what) const {
+    if (!generations())
+        throw Error(std::string(what) + ": rule " + cfg_.rule.str() + " has two states; the state calls are for Generations rules "
+                    "(B<digits>/S<digits>/C<n>, Simulation(rule=\"B2/S345/C4\"), GOL_RULE=B2/S345/C4)");
+}
+
+void Engine::need_two_states(const char* what) const {
+    if (generations())
+        throw Error(std::string(what) + ": not built for Generations rules in this version (the rule is " + cfg_.rule.str() + ")");
+}
+
+namespace {
+struct ViewPlane {  // the board's readers read plane p while this lives
+    ViewPlane(int& v, int p) : v_(v) { v_ = p; }
+    ~ViewPlane() { v_ = 0; }
+    int& v_;
+};
+}  // namespace
+
+std::vector<u8> Engine::state_window(i64 r0, i64 c0, i64 rows, i64 cols) {
+    need_generations("state_window()");
+    std::vector<u8> out = window(r0, c0, rows, cols);  // (the checks; state 1)
+    // decay plane m adds bit m of d = state - 1: a dying cell ends as 1 + d (no cell is alive and dying)
+    std::vector<u8> d(out.size(), 0);
+    for (int m = 0; m < cfg_.rule.decay_planes(); ++m) {
+        ViewPlane v(view_plane_, m + 1);
+        const std::vector<u8> plane = window(r0, c0, rows, cols);
+        for (size_t i = 0; i < d.size(); ++i) d[i] = (u8)(d[i] | (plane[i] << m));
+    }
+    for (size_t i = 0; i < out.size(); ++i)
+        if (d[i]) out[i] = (u8)(d[i] + 1);
+    return out;
+}
+
+std::vector<u8> Engine::state_tile() {
+    need_generations("state_tile()");
+    const i64 h = L_.h, w = L_.w, nw = L_.nw;
+    std::vector<u8> out((size_t)(h * w), 0), d((size_t)(h * w), 0);
+    for (int p = 0; p <= cfg_.rule.decay_planes(); ++p) {
+        ViewPlane v(view_plane_, p);
+        const std::vector<u64> words = tile_words();
+        std::vector<u8>& to = p == 0 ? out : d;  // plane 0: state 1; plane p: bit p - 1 of d
+        for (i64 r = 0; r < h; ++r)
+            for (i64 c = 0; c < w; ++c)
+                to[(size_t)(r * w + c)] |= (u8)(((words[(size_t)(r * nw + (c >> 6))] >> (c & 63)) & 1ull) << (p == 0 ? 0 : p - 1));
+    }
+    for (size_t i = 0; i < out.size(); ++i)
+        if (d[i]) out[i] = (u8)(d[i] + 1);
+    return out;
+}
+
+void Engine::set_state_tile(const std::vector<u8>& states) {
+    need_generations("set_state_tile()");
+    const i64 h = L_.h, w = L_.w, nw = L_.nw;
+    if ((i64)states.size() != h * w)
+        throw Error(strprintf("set_state_tile(): %zu states for a tile of %lld x %lld cells", states.size(), (long long)h, (long long)w));
+    for (size_t i = 0; i < states.size(); ++i)
+        if (states[i] >= cfg_.rule.states)
+            throw Error(strprintf("set_state_tile(): state %d at (%lld, %lld): rule %s has the states 0 .. %d", (int)states[i],
+                                  (long long)((i64)i / w), (long long)((i64)i % w), cfg_.rule.str().c_str(), (int)cfg_.rule.states - 1));
+    const int M = cfg_.rule.decay_planes();
+    std::vector<std::vector<u64>> planes((size_t)(M + 1), std::vector<u64>((size_t)(h * nw), 0));
+    for (i64 r = 0; r < h; ++r)
+        for (i64 c = 0; c < w; ++c) {
+            const unsigned s = states[(size_t)(r * w + c)];
+            const size_t at = (size_t)(r * nw + (c >> 6));
+            if (s == 1) planes[0][at] |= 1ull << (c & 63);
+            for (int m = 0; s >= 2 && m < M; ++m)
+                if (((s - 1) >> m) & 1u) planes[(size_t)(m + 1)][at] |= 1ull << (c & 63);
+        }
+    std::vector<const u64*> ptrs;
+    for (const auto& p : planes) ptrs.push_back(p.data());
+    write_planes_local(ptrs);
+}
+
+std::vector<u64> Engine::state_counts() {
+    need_generations("state_counts()");
+    std::vector<u64> counts((size_t)cfg_.rule.states, 0);
+    state_counts_local(counts.data());
+    return counts;  // (one rank: the tile is the board)
+}
+
+// ---------------------------------------------------------------------------------------------
 // Signatures (signature mode's record: census_host_ the populations, sig_host_ the signatures)
 // ---------------------------------------------------------------------------------------------
 
@@ -801,6 +910,7 @@ void Engine::stamp(const RlePattern& p, i64 r0, i64 c0, StampMode mode) {
     check_stamp(p, r0, c0);
     stamp_local(p, r0, c0, mode);
     if (cfg_.envelope) envelope_merge_local(false);  // E |= board: what the stamp removed stays in E
+    if (generations()) settle_decay_local();         // a stamped live cell is not dying as well
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -840,6 +950,7 @@ CellSource Engine::film_source(const u64* frames, i64 words, i64 n) const {
 }
 
 void Engine::read_tile_cells(const CellBuffer& dst) {
+    need_two_states("read_tile_cells()");
     need_cells(dst, L_.h * L_.w, "read_tile_cells()");
     check_cell_pointer(dst, "read_tile_cells()");
     read_rect_cells(0, 0, L_.h, L_.w, dst);
@@ -854,6 +965,7 @@ void Engine::read_envelope_cells(const CellBuffer& dst) {
 }
 
 void Engine::write_tile_cells(const CellBuffer& src) {
+    need_two_states("write_tile_cells()");
     need_cells(src, L_.h * L_.w, "write_tile_cells()");
     check_cell_pointer(src, "write_tile_cells()");
     write_tile_cells_local(src);
@@ -861,6 +973,7 @@ void Engine::write_tile_cells(const CellBuffer& src) {
 }
 
 void Engine::read_window_cells(i64 r0, i64 c0, i64 rows, i64 cols, const CellBuffer& dst) {
+    need_two_states("read_window_cells()");
     if (t_->size() > 1)
         throw Error(strprintf("read_window_cells(): this job has %d ranks; a window is unpacked on the device for one rank "
                               "only (use window())", t_->size()));
@@ -943,6 +1056,7 @@ Engine::MatchResult Engine::match(const std::vector<std::pair<int, MatchTemplate
 }
 
 void Engine::match_cells(const std::vector<std::pair<int, MatchTemplate>>& ts, const CellBuffer& dst) {
+    need_two_states("match_cells()");
     check_match(ts, "match_cells()");
     need_cells(dst, L_.h * L_.w, "match_cells()");
     check_cell_pointer(dst, "match_cells()");
@@ -962,8 +1076,9 @@ namespace {
 class CpuEngine : public Engine {
    public:
     CpuEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transport> t) : Engine(g, c, std::move(t)) {
-        a_.assign((size_t)L_.words(), 0);
-        b_.assign((size_t)L_.words(), 0);
+        planes_ = 1 + cfg_.rule.decay_planes();  // (a Generations rule: the decay planes follow the live plane)
+        a_.assign((size_t)(planes_ * L_.words()), 0);
+        b_.assign((size_t)(planes_ * L_.words()), 0);
         if (cfg_.envelope) env_.assign((size_t)L_.words(), 0);
         cur_ = a_.data();
         oth_ = b_.data();
@@ -978,10 +1093,23 @@ class CpuEngine : public Engine {
     }
     void set_tile_words(const std::vector<u64>& dense) override {
         if ((i64)dense.size() != L_.h * L_.nw) throw Error("set_tile_words: wrong size");
-        cpu::insert_words(cur_, L_, dense.data());
-        refresh_local(cur_);
+        write_planes_local({dense.data()});
         if (cfg_.envelope) envelope_reset();
     }
+    // the live plane, then the decay planes (a plane that is not given: zeros)
+    void write_planes_local(const std::vector<const u64*>& planes) override {
+        const std::vector<u64> zeros((size_t)(L_.h * L_.nw), 0);
+        for (i64 p = 0; p < planes_; ++p)
+            cpu::insert_words(cur_ + p * L_.words(), L_, (size_t)p < planes.size() && planes[(size_t)p] ? planes[(size_t)p] : zeros.data());
+        refresh_local(cur_);
+    }
+    void settle_decay_local() override {
+        for (i64 p = 1; p < planes_; ++p)
+            for (i64 r = 0; r < L_.h; ++r)
+                for (i64 c = 0; c < L_.nw; ++c) cur_[p * L_.words() + L_.index(r, c)] &= ~cur_[L_.index(r, c)];
+        refresh_local(cur_);
+    }
+    void state_counts_local(u64* counts) override { cpu::state_counts(cur_, L_, L_.words(), cfg_.rule, counts); }
     std::pair<u64, u64> local_reduce() override {
         return {cpu::population(view_buf(), L_),
                 cpu::fingerprint(view_buf(), L_, g_.row0, g_.word0(), g_.global_words())};
@@ -1088,13 +1216,16 @@ class CpuEngine : public Engine {
 
     void do_init(const PatternSpec& p) override {
         cpu::init_tile(cur_, L_, g_, p);
-        std::fill(oth_, oth_ + L_.words(), 0);
+        std::fill(cur_ + L_.words(), cur_ + planes_ * L_.words(), 0);  // (the decay planes: nothing is dying)
+        std::fill(oth_, oth_ + planes_ * L_.words(), 0);
         refresh_local(cur_);
     }
 
     void refresh_local(u64* buf) {
-        if (self_x()) cpu::fill_ghost_cols_wrap(buf, L_, 0, L_.h);
-        if (self_y() && !cfg_.compat) cpu::fill_ghost_rows_wrap(buf, L_);
+        for (i64 p = 0; p < planes_; ++p) {
+            if (self_x()) cpu::fill_ghost_cols_wrap(buf + p * L_.words(), L_, 0, L_.h);
+            if (self_y() && !cfg_.compat) cpu::fill_ghost_rows_wrap(buf + p * L_.words(), L_);
+        }
     }
 
     void exchange(int k) {
@@ -1133,7 +1264,8 @@ class CpuEngine : public Engine {
     void do_superstep(int k) override {
         if (!cfg_.compat) {
             exchange(k);
-            if (self_y()) cpu::fill_ghost_rows_wrap(cur_, L_);
+            if (self_y())
+                for (i64 p = 0; p < planes_; ++p) cpu::fill_ghost_rows_wrap(cur_ + p * L_.words(), L_);
         }
         u64 *counts = nullptr, *sigs = nullptr;
         if (cfg_.census || cfg_.signature) {  // this rank's own cells after each of the k generations
@@ -1158,9 +1290,10 @@ class CpuEngine : public Engine {
             dens = cpu::DensityOut{&density_geo_, density_host_.data() + (density_host_.size() - add)};
         }
         u64* res = cpu::superstep(cur_, oth_, L_, k, cfg_.rule, place, counts, sigs, film, dens,
-                                  cfg_.envelope ? env_.data() : nullptr);
+                                  cfg_.envelope ? env_.data() : nullptr, L_.words());
         if (res != cur_) std::swap(cur_, oth_);
-        if (self_x()) cpu::fill_ghost_cols_wrap(cur_, L_, 0, L_.h);
+        if (self_x())
+            for (i64 p = 0; p < planes_; ++p) cpu::fill_ghost_cols_wrap(cur_ + p * L_.words(), L_, 0, L_.h);
     }
 
     void do_set_compat_halos(const std::vector<u64>& above, const std::vector<u64>& below) override {
@@ -1179,7 +1312,8 @@ class CpuEngine : public Engine {
     }
 
    private:
-    const u64* view_buf() const { return view_env_ ? env_.data() : cur_; }
+    const u64* view_buf() const { return view_env_ ? env_.data() : cur_ + view_plane_ * L_.words(); }
+    i64 planes_ = 1;  // 1 + M under a Generations rule: a_ and b_ hold that many boards, L_.words() apart
     std::vector<u64> a_, b_, snap_;
     std::vector<u64> env_;  // envelope mode: E in the board's layout
     std::vector<u64> match_bits_;  // match(): the last bitmap, h x nw natural-order words

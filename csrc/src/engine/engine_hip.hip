@@ -77,6 +77,11 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
     if (cfg_.envelope && cfg_.kernel_depth > hipk::max_envelope_depth(cfg_.rule.nbhd))
         throw Error(strprintf("envelope: kernel_depth %d exceeds the envelope kernel's deepest pass, %d generations (GOL_KERNEL_DEPTH)",
                               cfg_.kernel_depth, hipk::max_envelope_depth(cfg_.rule.nbhd)));
+    // A Generations rule runs step_gen in the same way, at the depths its plane count allows.
+    if (generations() && cfg_.kernel_depth > hipk::max_generations_depth(states()))
+        throw Error(strprintf("kernel_depth %d exceeds the Generations kernel's deepest pass with %d states (rule %s), %d generations "
+                              "(GOL_KERNEL_DEPTH)", cfg_.kernel_depth, states(), cfg_.rule.str().c_str(),
+                              hipk::max_generations_depth(states())));
     if (rule_ && kernel_ == "auto") kernel_ = "rule";  // (any other name is refused below)
     hipk::ensure_trash();  // before any launch or graph capture
     // Kernel pass depth K (generations per HBM pass) vs halo depth R (generations per
@@ -116,7 +121,10 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
     if (R != L_.R) L_ = Layout(L_.h, L_.w, R);
     stats_.depth = R;
     // slack rows: the temporal kernel prefetches 3 (shallow passes: 6) rows past a segment's last input row
-    const size_t bytes = (size_t)(L_.words() + hipk::kSlackRows * L_.pitch) * 8;
+    // (a Generations rule: 1 + M such boards per buffer, the decay planes behind the live plane)
+    planes_ = 1 + cfg_.rule.decay_planes();
+    plane_words_ = L_.words() + hipk::kSlackRows * L_.pitch;
+    const size_t bytes = (size_t)planes_ * (size_t)plane_words_ * 8;
     for (int i = 0; i < 2; ++i) HIP_CHECK(hipMalloc(&buf_[i], bytes));
     alloc_bytes_ = bytes;
     if (cfg_.envelope && hipMalloc(&d_env_, bytes) != hipSuccess) {  // one more board-sized buffer
@@ -262,7 +270,7 @@ HipEngine::~HipEngine() {
         if (q) hipFree(q);
     for (void* p : deferred_free_) hipFree(p);
     for (void* p : {(void*)d_view_, (void*)d_grid_, (void*)d_pat_, (void*)d_census_, (void*)d_snap_, (void*)d_env_,
-                    (void*)d_match_, (void*)d_match_cnt_, (void*)d_match_pos_})
+                    (void*)d_match_, (void*)d_match_cnt_, (void*)d_match_pos_, (void*)d_states_})
         if (p) hipFree(p);
     if (h_view_) hipHostFree(h_view_);
     hipFree(d_red_);
@@ -302,20 +310,60 @@ void HipEngine::set_tile_words(const std::vector<u64>& dense) {
     sub_current_ = false;  // the canonical board is rewritten: sub-tiles reload at the next run()
     canon_stale_ = false;
     if ((i64)dense.size() != L_.h * L_.nw) throw Error("set_tile_words: wrong size");
+    write_planes_local({dense.data()});  // (a Generations rule: the decay planes are zeroed)
+    if (cfg_.envelope) envelope_reset();
+}
+
+// The tile's planes from dense natural-order words: the live plane, then the decay planes of a Generations rule (a
+// plane that is not given: zeros), and the ghosts of every plane.
+void HipEngine::write_planes_local(const std::vector<const u64*>& planes) {
+    sub_current_ = false;
+    canon_stale_ = false;
     synchronize();
-    std::vector<u64> m = dense;
-    for (i64 r = 0; r < L_.h; ++r)
-        for (i64 c = 0; c < L_.nw; ++c) {
-            u64& x = m[(size_t)(r * L_.nw + c)];
-            x = split_word(x & L_.mask(c));
-        }
-    HIP_CHECK(hipMemcpy2DAsync(buf_[cur_] + L_.index(0, 0), (size_t)L_.pitch * 8, m.data(), (size_t)L_.nw * 8,
-                               (size_t)L_.nw * 8, (size_t)L_.h, hipMemcpyHostToDevice, s_comp_));
-    HIP_CHECK(hipStreamSynchronize(s_comp_));  // m is pageable and goes out of scope
+    std::vector<u64> m((size_t)(L_.h * L_.nw));
+    for (int p = 0; p < planes_; ++p) {
+        const u64* dense = (size_t)p < planes.size() ? planes[(size_t)p] : nullptr;
+        for (i64 r = 0; r < L_.h; ++r)
+            for (i64 c = 0; c < L_.nw; ++c) {
+                const size_t at = (size_t)(r * L_.nw + c);
+                m[at] = dense ? split_word(dense[at] & L_.mask(c)) : 0;
+            }
+        HIP_CHECK(hipMemcpy2DAsync(buf_[cur_] + p * plane_words_ + L_.index(0, 0), (size_t)L_.pitch * 8, m.data(), (size_t)L_.nw * 8,
+                                   (size_t)L_.nw * 8, (size_t)L_.h, hipMemcpyHostToDevice, s_comp_));
+        HIP_CHECK(hipStreamSynchronize(s_comp_));  // m is pageable and is reused
+    }
     post(buf_[cur_], s_comp_);
     mark_ready();
     synchronize();
-    if (cfg_.envelope) envelope_reset();
+}
+
+// After a stamp under a Generations rule: the decay counter of every live cell cleared (aux_kernels.hip).  The board is
+// canonical and the streams are drained where this is called, as for envelope_merge_local.
+void HipEngine::settle_decay_local() {
+    sync_canonical();
+    synchronize();
+    hipk::launch_settle_decay(buf_[cur_], L_, plane_words_, cfg_.rule, s_comp_);
+    HIP_CHECK(hipGetLastError());
+    post(buf_[cur_], s_comp_);
+    mark_ready();
+    synchronize();
+}
+
+// counts[s] += the tile's cells in state s: k_state_counts adds into C striped slots, the host adds the stripes up.
+void HipEngine::state_counts_local(u64* counts) {
+    sync_canonical();
+    synchronize();
+    const size_t words = (size_t)states() * hipk::kCensusSlotWords;
+    if (!d_states_) HIP_CHECK(hipMalloc(&d_states_, (size_t)Rule::kMaxStates * hipk::kCensusSlotWords * sizeof(u64)));
+    HIP_CHECK(hipMemsetAsync(d_states_, 0, words * sizeof(u64), s_comp_));
+    hipk::launch_state_counts(buf_[cur_], L_, plane_words_, cfg_.rule, d_states_, s_comp_);
+    HIP_CHECK(hipGetLastError());
+    std::vector<u64> raw(words);
+    HIP_CHECK(hipMemcpyAsync(raw.data(), d_states_, words * sizeof(u64), hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+    for (int s = 0; s < states(); ++s)
+        for (int st = 0; st < hipk::kCensusStripes; ++st)
+            counts[s] += raw[(size_t)s * hipk::kCensusSlotWords + (size_t)st * hipk::kCensusStripeWords];
 }
 
 // Envelope mode's reset and stamp follow-up (aux_kernels.hip): the board is canonical and the streams are drained
@@ -546,7 +594,7 @@ void HipEngine::finish_init() {
     if (!split_ && !dual_ && kern_[0] == "pipe")
         stats_.kernel = strprintf("pipe@%d(%dx%d,%d/CU)", pipe_k_, pipe_cur_.nw - 1, pipe_cur_.l, pipe_cur_.wg);
     if (rule_) {
-        const std::string rk = strprintf(cfg_.envelope ? "envelope@%d" : cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", kdepth_);
+        const std::string rk = strprintf(generations() ? "gen@%d" : cfg_.envelope ? "envelope@%d" : cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", kdepth_);
         stats_.kernel = split_ ? rk + "+boundary:" + rk : rk;
     }
     if (res_) {
@@ -573,7 +621,7 @@ void HipEngine::finish_init() {
                 const PassKernel pk = pass_kernel(kind, ps[j]);
                 c += (j ? "+" : "") + (pk == PK_PIPE   ? strprintf("pipe@%d(%dx%d,%d/CU)", ps[j], g->nw - 1, g->l, g->wg)
                                        : pk == PK_TILE ? strprintf("tile@%d", ps[j])
-                                       : pk == PK_RULE ? strprintf(cfg_.envelope ? "envelope@%d" : cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", ps[j])
+                                       : pk == PK_RULE ? strprintf(generations() ? "gen@%d" : cfg_.envelope ? "envelope@%d" : cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", ps[j])
                                                        : strprintf("temporal@%d", ps[j]));
             }
             tn += strprintf("%scut%d=%s", tn.empty() ? "" : " ", k, c.c_str());
@@ -839,7 +887,9 @@ void HipEngine::launch(int kind, int k, i64 e, const u64* src, u64* dst, hipStre
             pipe_used_ = true;
         } else if (pk == PK_RULE) {
             const hipk::BoardEdges edges{g_.row0, g_.dec.H, g_.word0(), g_.dec.W};
-            if (cfg_.envelope) {
+            if (generations()) {  // (src and dst are live planes of boards allocated here: plane_words_ apart)
+                hipk::launch_step_gen(k, cfg_.rule, edges, dead_edges(), L_.w, src, dst, plane_words_, plane_words_, p.d, p.waves, sp, s);
+            } else if (cfg_.envelope) {
                 hipk::launch_step_envelope(k, cfg_.rule, edges, dead_edges(), L_.w, src, dst, env_at_, p.d, p.waves, sp, s);
             } else if (cfg_.density_film.on) {
                 DensityGeo grid = density_geo_;  // (a block larger than the board counts what one of the board's size does)

@@ -321,7 +321,9 @@ class HipEngine : public Engine {
     }
     // The streaming kernel of this engine: step_rule under a rule (rule_), else step_temporal.
     // (in census mode step_census, at its own depths, on either boundary)
+    // (under a Generations rule step_gen, at the depths of its plane count)
     bool depth_ok(int k) const {
+        if (generations()) return k >= 1 && k <= hipk::max_generations_depth(states());
         if (cfg_.envelope) return k >= 1 && k <= hipk::max_envelope_depth(cfg_.rule.nbhd);
         if (cfg_.density_film.on) return k >= 1 && k <= hipk::max_density_depth(cfg_.rule.nbhd);
         if (cfg_.film.on) return k >= 1 && k <= hipk::max_film_depth(cfg_.rule.nbhd);
@@ -330,6 +332,7 @@ class HipEngine : public Engine {
         return rule_ ? hipk::rule_depth_supported(k, cfg_.rule.nbhd) : hipk::step_depth_supported(k);
     }
     int max_depth() const {
+        if (generations()) return hipk::max_generations_depth(states());
         if (cfg_.envelope) return hipk::max_envelope_depth(cfg_.rule.nbhd);
         if (cfg_.density_film.on) return hipk::max_density_depth(cfg_.rule.nbhd);
         if (cfg_.film.on) return hipk::max_film_depth(cfg_.rule.nbhd);
@@ -338,6 +341,7 @@ class HipEngine : public Engine {
         return rule_ ? hipk::max_rule_depth(cfg_.rule.nbhd) : hipk::max_step_depth();
     }
     int blocks_per_cu(int k, u32 flags) const {
+        if (generations()) return hipk::generations_blocks_per_cu(k, flags, dead_edges(), states());
         if (cfg_.envelope) return hipk::envelope_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
         if (cfg_.density_film.on) return hipk::density_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
         if (cfg_.film.on) return hipk::film_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
@@ -526,9 +530,11 @@ class HipEngine : public Engine {
     void launch(int kind, int k, i64 e, const u64* src, u64* dst, hipStream_t s, u32 xflags = 0);
 
     // Ghost words for widths that are not a multiple of 64 when the tile is its own E/W neighbour.
+    // (every plane of a Generations board: the decay planes wrap like the live plane)
     void post(u64* buf, hipStream_t s, i64 rem = 0) {
         const i64 e = self_y() ? 0 : rem;
-        if (self_x() && !L_.aligned()) hipk::launch_fill_ghost_cols(buf, L_, -e, L_.h + e, s);
+        if (self_x() && !L_.aligned())
+            for (int p = 0; p < planes_; ++p) hipk::launch_fill_ghost_cols(buf + p * plane_words_, L_, -e, L_.h + e, s);
     }
 
     // ----- halo exchange -----
@@ -798,7 +804,18 @@ class HipEngine : public Engine {
     // run() that is no timing sample, else null: every other launch (the init-time autotune, schedule timing, the
     // hinted run's prediction) hands step_envelope a null envelope and leaves E untouched.
     void envelope_merge_local(bool reset) override;
-    const u64* view_buf() const { return view_env_ ? d_env_ : buf_[cur_]; }  // what the readers read
+    const u64* view_buf() const { return view_env_ ? d_env_ : buf_[cur_] + view_plane_ * plane_words_; }  // what the readers read
+    // ----- Generations rules -----
+    // buf_[0] and buf_[1] hold planes_ = 1 + M boards each, plane_words_ words apart (a board with its halo and slack
+    // rows): the live plane, then the decay planes.  Every launch() hands step_gen the live planes of its src and dst,
+    // and the kernel finds the others from plane_words_, so the timing launches on the scratch buffer, the buffer flip
+    // and predict_run's snapshot of alloc_bytes_ cover the decay planes without bookkeeping of their own.
+    void write_planes_local(const std::vector<const u64*>& planes) override;
+    void settle_decay_local() override;
+    void state_counts_local(u64* counts) override;
+    int planes_ = 1;
+    i64 plane_words_ = 0;
+    u64* d_states_ = nullptr;  // state_counts(): C slots of kCensusSlotWords words
     u64* d_env_ = nullptr;
     u64* env_at_ = nullptr;
     u64* d_snap_ = nullptr;  // snapshot(): a third board buffer (alloc_bytes_), allocated on first use

@@ -122,6 +122,54 @@ __global__ void k_envelope_merge(u64* __restrict__ env, const u64* __restrict__ 
     }
 }
 
+// Generations rules: the census of the states.  A lane forms each state's mask from the planes of the words it owns
+// (storage mask on the tile's last word) and popcounts it; the C counts are summed over the wave and go, one 64-bit
+// atomic per state and wave, to the state's slot in the census's stripe layout (kCensusSlotWords words per state).
+__global__ __launch_bounds__(256) void k_state_counts(const u64* __restrict__ buf, i64 plane_stride, int M, int states, i64 pitch,
+                                                      int R, i64 h, i64 nw, i64 w, unsigned long long* __restrict__ out) {
+    u32 acc[Rule::kMaxStates];
+#pragma unroll
+    for (int s = 0; s < Rule::kMaxStates; ++s) acc[s] = 0;
+    const i64 n = h * nw;
+    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (i64)gridDim.x * blockDim.x) {
+        const i64 r = e / nw, c = e - r * nw;
+        const i64 at = (r + R) * pitch + c + 1;
+        const u64 own = storage_mask(c, w), A = buf[at] & own;
+        u64 d[3] = {0, 0, 0};
+#pragma unroll
+        for (int m = 0; m < 3; ++m)
+            if (m < M) d[m] = buf[(m + 1) * plane_stride + at] & own;  // (M: uniform)
+        acc[0] += (u32)__popcll(own & ~(A | d[0] | d[1] | d[2]));
+        acc[1] += (u32)__popcll(A);
+#pragma unroll
+        for (int s = 2; s < Rule::kMaxStates; ++s) {  // state s: d == s - 1 (counts past C - 1 stay 0: d <= C - 2)
+            const int v = s - 1;
+            acc[s] += (u32)__popcll((v & 1 ? d[0] : ~d[0]) & (v & 2 ? d[1] : ~d[1]) & (v & 4 ? d[2] : ~d[2]) & own);
+        }
+    }
+    const i64 wave = ((i64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const size_t stripe = (size_t)(wave & (kCensusStripes - 1)) * kCensusStripeWords;
+#pragma unroll
+    for (int s = 0; s < Rule::kMaxStates; ++s) {
+        u32 v = acc[s];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+        if ((threadIdx.x & 63) == 0 && v != 0 && s < states) atomicAdd(out + (size_t)s * kCensusSlotWords + stripe, (unsigned long long)v);
+    }
+}
+
+// Generations rules, after a stamp: no cell is alive and dying.  Every decay plane loses the live plane's cells over
+// the tile's own words (the ghosts follow with the caller's ghost fills).
+__global__ void k_settle_decay(u64* __restrict__ buf, i64 plane_stride, int M, i64 pitch, int R, i64 h, i64 nw) {
+    const i64 n = h * nw;
+    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (i64)gridDim.x * blockDim.x) {
+        const i64 r = e / nw, c = e - r * nw;
+        const i64 at = (r + R) * pitch + c + 1;
+        const u64 live = buf[at];
+        for (int m = 1; m <= M; ++m) buf[m * plane_stride + at] &= ~live;
+    }
+}
+
 unsigned grid_for(i64 n, int block = 256, i64 cap = 256 * 16) {
     i64 g = ceil_div(n, block);
     if (g < 1) g = 1;
@@ -166,6 +214,22 @@ void launch_reduce_board(const u64* buf, const Layout& L, i64 grow0, i64 gword0,
 void launch_envelope_merge(u64* env, const u64* board, const Layout& L, bool reset, hipStream_t s) {
     hipLaunchKernelGGL(k_envelope_merge, dim3(grid_for(L.h * L.nw)), dim3(256), 0, s, env, board, L.pitch, L.R, L.h, L.nw, L.w,
                        reset ? 1 : 0);
+}
+
+void launch_state_counts(const u64* buf, const Layout& L, i64 plane_stride, const Rule& rule, u64* out, hipStream_t s) {
+    if (!rule.generations() || plane_stride < L.words())
+        throw Error(strprintf("state_counts: rule %s with a plane stride of %lld words (a board has %lld)", rule.str().c_str(),
+                              (long long)plane_stride, (long long)L.words()));
+    hipLaunchKernelGGL(k_state_counts, dim3(grid_for(L.h * L.nw, 256, 2048)), dim3(256), 0, s, buf, plane_stride, rule.decay_planes(),
+                       (int)rule.states, L.pitch, L.R, L.h, L.nw, L.w, (unsigned long long*)out);
+}
+
+void launch_settle_decay(u64* buf, const Layout& L, i64 plane_stride, const Rule& rule, hipStream_t s) {
+    if (!rule.generations() || plane_stride < L.words())
+        throw Error(strprintf("settle_decay: rule %s with a plane stride of %lld words (a board has %lld)", rule.str().c_str(),
+                              (long long)plane_stride, (long long)L.words()));
+    hipLaunchKernelGGL(k_settle_decay, dim3(grid_for(L.h * L.nw)), dim3(256), 0, s, buf, plane_stride, rule.decay_planes(), L.pitch,
+                       L.R, L.h, L.nw);
 }
 
 void launch_naive_byte_step(const u8* src, u8* dst, i64 w, i64 h, const u8* above, const u8* below, int threads,

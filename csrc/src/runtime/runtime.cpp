@@ -201,6 +201,7 @@ EngineConfig engine_config(const Options& o, const std::string& backend, int dev
 // ---------------------------------------------------------------------------------------------
 
 void write_dumps(Engine& eng, FILE* fp) {
+    eng.need_two_states("write_dumps()");
     trace::Range range("gol.dump");
     const Geometry& g = eng.geometry();
     const Decomposition& d = g.dec;
@@ -309,6 +310,7 @@ void pread_all(int fd, void* buf, size_t n, off_t off, const std::string& name) 
 }  // namespace
 
 void save_checkpoint(Engine& eng, const std::string& prefix, u64 seed) {
+    eng.need_two_states("save_checkpoint()");
     trace::Range range("gol.checkpoint");
     const Geometry& g = eng.geometry();
     Transport& t = eng.transport();
@@ -368,6 +370,7 @@ void save_checkpoint(Engine& eng, const std::string& prefix, u64 seed) {
 }
 
 u64 load_checkpoint(Engine& eng, const std::string& prefix) {
+    eng.need_two_states("load_checkpoint()");
     const Geometry& g = eng.geometry();
     const std::string name = ckpt_name(prefix);
     const int fd = open(name.c_str(), O_RDONLY);
@@ -641,6 +644,18 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
         std::shared_ptr<Transport> t = make_data_transport(control, backend, o, device);
         EngineConfig ec = engine_config(o, backend, device);
         apply_threads_hint(ec, a.threads, rank == 0);
+        if (ec.rule.generations()) {  // (the same on every rank, before any engine exists)
+            const std::string rs = ec.rule.str();
+            if (a.on_off == 1)
+                throw Error("the dump (output_on_off = 1) is not built for Generations rules in this version (the rule is " + rs +
+                            "): a dump file holds two-state cells");
+            if (!o.rle_out.empty())
+                throw Error("GOL_RLE_OUT is not built for Generations rules in this version (the rule is " + rs +
+                            "): multi-state RLE is not written");
+            if (!o.restart.empty() || o.checkpoint_every > 0)
+                throw Error("checkpoints (GOL_RESTART, GOL_CHECKPOINT_EVERY) are not built for Generations rules in this version (the rule is " +
+                            rs + ")");
+        }
         ec.run_hint = o.checkpoint_every > 0 ? (u64)o.checkpoint_every : (u64)a.iterations;
         std::unique_ptr<Engine> eng = Engine::create(g, ec, t);
         if (o.verbose && rank == 0) fprintf(stderr, "[gol] %s\n", eng->describe().c_str());

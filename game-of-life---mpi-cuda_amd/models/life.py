@@ -52,6 +52,18 @@ class Simulation:
                   instead of Moore's eight: ``"B13/S13V"``, ``"B2/S34H"``.  B3/S23 runs the specialised bit-sliced kernels;
                   any other B0-free rule the generic ones (HIP: ``step_rule``, CPU: a bit-sliced count),
                   without ``compat``, ``subtiles=2`` or the B3/S23-only kernels.
+                  A third field makes a Generations rule: ``"B2/S345/C4"`` (also ``S.../B.../C<n>`` and the bare
+                  ``345/2/4``, survive / birth / states), 3 to 9 states: 0 dead, 1 alive, 2 .. C-1 dying.  A live cell
+                  that does not survive decays through the dying states, which count as no neighbour and cannot be born
+                  (``ops.numpy_generations`` is the definition).  :attr:`states` gives C; :meth:`board`, :meth:`window`
+                  and :meth:`set_board` then speak states, :meth:`state_counts` counts them, and :meth:`words`,
+                  :meth:`population`, :meth:`density`, :meth:`fingerprint`, :meth:`signature`, :meth:`snapshot`,
+                  :meth:`match` and :meth:`stamp` act on the live cells (state 1); a stamped cell is alive and not
+                  dying, ``replace`` and ``clear`` leave dying cells dying.  HIP: ``step_gen`` runs every pass
+                  (``stats()["kernel"]`` is ``gen@K``, eager launches, passes of at most
+                  ``max_generations_depth(C)`` generations).  One rank, Moore, no recording mode, ``compat``,
+                  ``subtiles=2``, ``self_exchange``, ``force_split`` or specialised kernel; checkpoints, ``save_rle``,
+                  dumps and the tensor calls are refused in this version.
     kernel_depth: generations per kernel pass (HIP; 0 = auto).  A superstep of halo_depth
                   generations runs as several kernel passes in 1-D (communication-avoiding halos).
     kernel:       HIP stencil kernel: ``"auto"`` (candidates timed at init), ``"temporal"``,
@@ -166,6 +178,7 @@ class Simulation:
         if boundary is None:  # (read per call, so a test or a driver can set it between simulations)
             boundary = os.environ.get("GOL_BOUNDARY", "torus")
         cfg.boundary = boundary  # (ValueError on anything but torus or dead, naming it)
+        self.states = int(_gol.parse_rule_states(cfg.rule))  # 2, or C of a Generations rule
         if cfg.boundary == "dead":
             if compat:
                 raise ValueError("compat=True with boundary dead: the reference is a torus")
@@ -307,6 +320,36 @@ class Simulation:
                     f"envelope: kernel_depth {kernel_depth} exceeds the envelope kernel's deepest pass, "
                     f"{_gol.max_envelope_depth()} generations"
                 )
+        if self.states > 2:  # a Generations rule: what this version does not run with one, each named
+            r = cfg.rule
+
+            def refuse(option: str, why: str):
+                raise ValueError(f"{option} with the Generations rule {r}: {why}")
+
+            if P > 1:
+                raise ValueError(f"the Generations rule {r} on {P} ranks: Generations rules run on one rank")
+            if cfg.census:
+                refuse("census=True", "the census kernel counts two-state boards")
+            if cfg.signature:
+                refuse("signature=True", "the signature kernel hashes two-state boards")
+            if cfg.film is not None:
+                refuse("film", "the film kernel stores two-state frames")
+            if cfg.density_film is not None:
+                refuse("density_film", "the density kernel counts two-state boards")
+            if envelope:
+                refuse("envelope=True", "the envelope kernel records two-state boards")
+            if bool(self_exchange):
+                refuse("self_exchange=True", "the exchange of the decay planes is not built")
+            if bool(force_split):
+                refuse("force_split=True", "the split schedule's exchange of the decay planes is not built")
+            if self.backend == "hip" and kernel not in ("auto", "rule"):
+                refuse(f"kernel {kernel!r}", "step_gen runs every pass (use auto or rule)")
+            if self.backend == "hip" and int(kernel_depth) > _gol.max_generations_depth(self.states):
+                refuse(
+                    f"kernel_depth {kernel_depth}",
+                    f"the Generations kernel's deepest pass with {self.states} states is "
+                    f"{_gol.max_generations_depth(self.states)} generations",
+                )
         cfg.envelope = bool(envelope)
         cfg.subtiles = int(subtiles)  # 2 / 0 / -1 auto: two sub-tiles per rank on two streams (HIP, 1-D)
         cfg.run_hint = int(run_hint)  # generations of the runs to come: one replay graph covers them
@@ -361,16 +404,37 @@ class Simulation:
         return self.engine.tile_words()
 
     def board(self) -> np.ndarray:
-        """Local tile as a (h, w) uint8 array of 0/1 cells."""
+        """Local tile as a (h, w) uint8 array of 0/1 cells; under a Generations rule, of the states 0 .. C-1."""
+        if self.states > 2:
+            return self.engine.state_tile()
         return unpack_words(self.words(), self.geometry.w)
 
     def set_board(self, cells: np.ndarray) -> None:
+        """The local tile from a (h, w) array of 0/1 cells; under a Generations rule, of states (a value >= C is a
+        ValueError that names it, and nothing is written)."""
         from ..ops.bitpack import pack_cells
 
         cells = np.asarray(cells)
         if cells.shape != (self.geometry.h, self.geometry.w):
             raise ValueError(f"expected a {(self.geometry.h, self.geometry.w)} board, got {cells.shape}")
+        if self.states > 2:
+            if cells.size and (int(cells.min()) < 0 or int(cells.max()) >= self.states):
+                bad = int(cells.max()) if int(cells.max()) >= self.states else int(cells.min())
+                raise ValueError(f"set_board: state {bad} on the board: rule {self.config.rule} has the states 0 .. {self.states - 1}")
+            self.engine.set_state_tile(np.ascontiguousarray(cells, dtype=np.uint8))
+            return
         self.engine.set_tile_words(pack_cells(cells))
+
+    def state_counts(self) -> np.ndarray:
+        """The cells of the global board in each state: a ``(C,)`` uint64 array (``[1]`` is :meth:`population`).  Needs
+        a Generations rule.  HIP: counted on the device, only the counts leave it."""
+        if self.states <= 2:
+            raise ValueError(f"state_counts() needs a Generations rule (B<digits>/S<digits>/C<n>); rule {self.config.rule} has two states")
+        return self.engine.state_counts()
+
+    def _two_states(self, what: str) -> None:
+        if self.states > 2:
+            raise ValueError(f"{what} is not built for Generations rules in this version (the rule is {self.config.rule})")
 
     # -- torch tensors (ops/tensors.py states the dtypes and the stream ordering) ----------------
     # On the HIP backend every tensor argument and result is a CUDA tensor on cuda:<device> and the cells never leave the
@@ -395,6 +459,7 @@ class Simulation:
         stream before the call returns."""
         from ..ops import tensors
 
+        self._two_states("board_tensor()")
         t = tensors.result((self.geometry.h, self.geometry.w), dtype, self._tensor_device(), out, "board_tensor")
         tensors.sync(t)
         self.engine.read_tile_cells(*tensors.handle(t))
@@ -406,6 +471,7 @@ class Simulation:
         current torch stream is synchronised before the engine reads the tensor."""
         from ..ops import tensors
 
+        self._two_states("load_tensor()")
         t = tensors.check_input(cells, (self.geometry.h, self.geometry.w), self._tensor_device(), "load_tensor")
         tensors.sync(t)
         self.engine.write_tile_cells(*tensors.handle(t))
@@ -428,6 +494,7 @@ class Simulation:
         from ..ops import tensors
 
         r0, c0, rows, cols = int(r0), int(c0), int(rows), int(cols)
+        self._two_states("window_tensor()")
         self._one_rank("window_tensor")
         H, W = self.decomposition.H, self.decomposition.W
         if not (1 <= rows <= H and 1 <= cols <= W):
@@ -644,6 +711,8 @@ class Simulation:
         board's size.  On a bounded board (``boundary="dead"``) it must lie inside the board.  On the HIP backend
         only the window's bytes leave the device."""
         self._check_inside("window", int(r0), int(c0), int(rows), int(cols))
+        if self.states > 2:  # (a Generations rule: the states 0 .. C-1)
+            return self.engine.state_window(int(r0), int(c0), int(rows), int(cols))
         return self.engine.window(int(r0), int(c0), int(rows), int(cols))
 
     def _check_inside(self, what: str, r0: int, c0: int, rows: int, cols: int) -> None:
@@ -745,6 +814,7 @@ class Simulation:
         0.  Arguments as :meth:`match`; dtype, ``out``, stream ordering and errors as :meth:`board_tensor`."""
         from ..ops import tensors
 
+        self._two_states("match_tensor()")
         ts = self._match_templates("match_tensor", pattern_or_template, margin, orientations)
         t = tensors.result((self.geometry.h, self.geometry.w), dtype, self._tensor_device(), out, "match_tensor")
         tensors.sync(t)
@@ -776,6 +846,7 @@ class Simulation:
         (``rule = B3/S23:P<W>,<H>``).  Collective; rank 0 writes."""
         from ..ops.rle import pattern_from_cells
 
+        self._two_states("save_rle()")  # (multi-state RLE is not written)
         H, W = self.decomposition.H, self.decomposition.W
         r0, c0, rows, cols = window if window is not None else (0, 0, H, W)
         cells = self.window(r0, c0, rows, cols)
@@ -820,6 +891,7 @@ class Simulation:
     # -- I/O -------------------------------------------------------------------------------
     def dump(self, path: Optional[str] = None) -> str:
         """Write this rank's reference-format dump file (collective); returns the path."""
+        self._two_states("dump()")
         if path is None:
             path = _gol.dump_filename(self.geometry.rank, self.decomposition.P)
         _gol.write_dumps(self.engine, path)
@@ -831,8 +903,10 @@ class Simulation:
         The file does not depend on the decomposition: :meth:`restore` works on any rank count or
         grid with the same global board size.
         """
+        self._two_states("checkpoint()")
         _gol.save_checkpoint(self.engine, prefix, self.pattern.seed if self.pattern else 0)
 
     def restore(self, prefix: str) -> int:
         """Load this rank's rectangle of ``<prefix>.gol``; returns the snapshot's generation."""
+        self._two_states("restore()")
         return int(_gol.load_checkpoint(self.engine, prefix))

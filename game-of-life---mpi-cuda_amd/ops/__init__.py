@@ -7,14 +7,17 @@ from .oracle import (  # noqa: F401
     numpy_density_film,
     numpy_envelope,
     numpy_film,
+    numpy_generations,
     numpy_signature,
     numpy_signatures,
     numpy_soup_settle,
     numpy_step,
     numpy_step_rule,
     numpy_step_rule_bounded,
+    parse_generations_rule,
     parse_rule,
     parse_rule_nbhd,
+    parse_rule_states,
     quirk_model,
     random_board,
     rule_string,

@@ -165,6 +165,78 @@ def numpy_step_rule_bounded(board: np.ndarray, rule, generations: int = 1) -> np
     return b
 
 
+def parse_generations_rule(rule) -> tuple:
+    """A rule string as ``(birth, survive, states)``: a Generations rule ``B<digits>/S<digits>/C<n>``, ``S.../B.../C<n>``
+    (either case) or the bare ``<survive digits>/<birth digits>/<n>`` with ``n`` from 2 to 9 and no leading zero, or a
+    two-state Moore rule as :func:`parse_rule` takes it (``states`` 2).  ``C2`` is the two-state rule.  A parser of its
+    own, independent of the native one.  A ``V`` or ``H`` suffix together with ``/C`` is refused, and B0, as in the engine."""
+    if not isinstance(rule, str):
+        birth, survive, states = (int(v) for v in rule)
+        if not (0 <= birth < 512 and 0 <= survive < 512 and 2 <= states <= 9) or birth & 1:
+            raise ValueError(f"invalid rule {rule!r}: masks have bits 0..8 (B0 is out of scope), states run from 2 to 9")
+        return birth, survive, states
+    text = _RULE_ALIASES.get(rule.lower(), rule.lower())
+    parts = text.split("/")
+    if len(parts) == 3:
+        if all(p.isdigit() or p == "" for p in parts) and parts[2] != "":  # bare: survive / birth / states
+            parts = ["b" + parts[1], "s" + parts[0], "c" + parts[2]]
+        count = parts[2]
+        if count[:1] != "c" or not count[1:].isdigit() or (len(count) > 2 and count[1] == "0") or not 2 <= int(count[1:]) <= 9:
+            raise ValueError(f"invalid rule {rule!r}: the third field is C<n>, n from 2 to 9 without leading zeros")
+        if parts[1][-1:] in ("v", "h"):
+            raise ValueError(f"invalid rule {rule!r}: a V or H suffix together with /C")
+        birth, survive, nbhd = parse_rule_nbhd("/".join(parts[:2]))
+        return birth, survive, int(count[1:])
+    birth, survive, nbhd = parse_rule_nbhd(rule)
+    if nbhd:
+        raise ValueError(f"invalid rule {rule!r}: Generations rules count the Moore neighbourhood")
+    return birth, survive, 2
+
+
+def parse_rule_states(rule) -> int:
+    """The states of a rule string: 2 for a life-like rule (any neighbourhood), C for a Generations rule
+    ``B<digits>/S<digits>/C<n>``."""
+    if isinstance(rule, str) and rule.count("/") < 2:
+        parse_rule_nbhd(rule)
+        return 2
+    return parse_generations_rule(rule)[2]
+
+
+def numpy_generations(board: np.ndarray, rule, gens: int, boundary: str = "torus") -> np.ndarray:
+    """The oracle of the Generations rules: ``gens`` generations of the state array ``board`` (uint8, states 0 .. C-1)
+    under ``rule`` (a string, or ``(birth, survive, states)``) and returns the state array.  State 0 is dead, 1 alive,
+    2 .. C-1 dying.  Only state 1 counts as a neighbour (Moore; ``boundary`` ``"torus"``: ``np.roll``, ``"dead"``: zero
+    padding).  ``0 -> 1`` iff the count is in B; ``1 -> 1`` iff it is in S, else ``1 -> 2``; ``s -> s + 1`` for
+    ``2 <= s < C-1`` and ``C-1 -> 0`` whatever the count.  With two states this is the life-like rule."""
+    birth, survive, states = parse_generations_rule(rule)
+    if boundary not in ("torus", "dead"):
+        raise ValueError(f"boundary must be torus or dead, got {boundary!r}")
+    b = np.asarray(board, dtype=np.uint8)
+    if b.ndim != 2:
+        raise ValueError(f"a board is a 2-D array, got shape {b.shape}")
+    if b.size and int(b.max()) >= states:
+        raise ValueError(f"state {int(b.max())} on the board: the rule has the states 0 .. {states - 1}")
+    H, W = b.shape
+    for _ in range(int(gens)):
+        live = (b == 1).astype(np.int32)
+        if boundary == "torus":
+            n = sum(np.roll(np.roll(live, dy, axis=0), dx, axis=1) for dy in (-1, 0, 1) for dx in (-1, 0, 1) if dy or dx)
+        else:
+            pad = np.zeros((H + 2, W + 2), dtype=np.int32)
+            pad[1:-1, 1:-1] = live
+            n = sum(pad[dy : dy + H, dx : dx + W] for dy in (0, 1, 2) for dx in (0, 1, 2) if (dy, dx) != (1, 1))
+        born = (b == 0) & (((birth >> n) & 1) == 1)
+        stays = (b == 1) & (((survive >> n) & 1) == 1)
+        nxt = np.zeros_like(b)
+        nxt[born | stays] = 1
+        if states > 2:
+            nxt[(b == 1) & ~stays] = 2
+            dying = (b >= 2) & (b < states - 1)
+            nxt[dying] = b[dying] + 1  # (C-1 -> 0: left at zero)
+        b = nxt
+    return b
+
+
 def numpy_census(board: np.ndarray, rule, gens: int, bounded: bool = False, return_board: bool = False):
     """The populations after generations ``1 .. gens`` of ``board`` under ``rule`` as a uint64 array (the oracle of
     the engines' census mode), on the torus or, ``bounded``, on a board with dead edges.  One generation of
