@@ -73,6 +73,11 @@ u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule = Rule()
 // ghost row is needed: a dying cell there cannot be born); no cell is alive and dying.  counts, sigs, film, density and
 // envelope must be off.  state_counts: counts[s] += the tile's own cells in state s, s = 0 .. rule.states - 1.
 void state_counts(const u64* buf, const Layout& L, i64 plane_stride, const Rule& rule, u64* counts);
+// Larger than Life rules (rule.range > 0, gol/rule.hpp): superstep steps one generation at a time, any k >= 1, on a tile
+// that is the whole board (one rank: edges.row0 and word0 are 0, a bounded board's size is the tile's) of at least
+// 2 range + 1 cells either way.  It reads the tile's own cells only (the torus by indexing, a bounded board by zeros
+// around it) and writes rows [0, h) whole, ghost words zero.  Row-wise sums over unpacked cells: an oracle, not fast.
+// counts, sigs, film, density and envelope must be off.
 // envelope (envelope mode; nullptr: none): a buffer in layout L; after every generation the tile's own cells (rows
 // [0, h), words [0, nw), storage mask on the last word) are ORed into it.  envelope_or does that for one board.
 void envelope_or(u64* envelope, const u64* board, const Layout& L);

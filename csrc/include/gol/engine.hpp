@@ -126,8 +126,8 @@ struct EngineStats {
     int predicted_gens = 0;     // generations of the timed supersteps behind it
     double t_exchange_ms = 0;  // profile only
     double t_compute_ms = 0;   // profile only
-    std::string kernel;        // stencil kernel in use (HIP: temporal | tile | lds | rule@K | gen@K; CPU: cpu)
-    std::string rule;          // the rule, canonical (B3/S23; a Generations rule: B2/S345/C4)
+    std::string kernel;        // stencil kernel in use (HIP: temporal | tile | lds | rule@K | gen@K | ltl@1; CPU: cpu)
+    std::string rule;          // the rule, canonical (B3/S23; a Generations rule: B2/S345/C4; LtL: R5,C0,M1,S34..58,B34..45,NM)
     int states = 2;            // its states: 2, or C of a Generations rule
     std::string boundary;      // torus | dead
     bool census = false;       // census mode
@@ -216,6 +216,13 @@ class Engine {
     std::vector<u64> state_counts();                       // C counts: the cells of the board in each state
     // Throws, naming the call and the rule, under a Generations rule: what is not built for them in this version.
     void need_two_states(const char* what) const;
+    // ----- Larger than Life rules (EngineConfig::rule with range > 0; gol/rule.hpp) -----
+    // Two states on the ordinary board: every reader and writer of the board works unchanged.  One rank; a superstep is
+    // one generation (stats.depth and stats.kernel_depth are 1) although the layout's halo depth is the rule's range, the
+    // depth of the generation's dependency cone.  need_rule_code throws, naming the call and the rule, under such a rule:
+    // checkpoints, which need Rule::code().
+    bool ltl() const { return cfg_.rule.ltl(); }
+    void need_rule_code(const char* what) const;
 
     // ----- envelope (EngineConfig::envelope) -----
     // E = board(start) | board(start + 1) | ... | board(generation()), cell by cell, with start the generation of the

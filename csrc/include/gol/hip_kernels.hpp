@@ -23,6 +23,9 @@
 //   step_gen<K, M>    — Generations rules (B/S/C): step_rule / step_rule_bounded on the live plane with the dying
 //                       cells' decay counter, M more bit planes, carried through the levels (generations_kernel.hip;
 //                       K = 1 .. max_generations_depth(C); with k_state_counts and k_settle_decay in aux_kernels.hip).
+//   step_ltl<R>       — Larger than Life rules (range R = 1 .. 7, the box neighbourhood, count intervals): one generation
+//                       per pass on the same streaming wave, a bit-sliced (2R+1)^2 box sum from shifted copies, a ring
+//                       of horizontal sums and a running column sum, four bit-sliced threshold compares (ltl_kernel.hip).
 //   step_soups<M>     — soup batches (gol/soups.hpp), beside the engine: many independent 64 M x 64 M tori per launch, one
 //                       wave64 per soup with the board in registers, settled inside the kernel (soup_kernel.hip; its host
 //                       API is src/hip/soup_kernel.hpp).
@@ -195,6 +198,14 @@ int max_generations_depth(int states);
 int generations_blocks_per_cu(int k, u32 flags, bool bounded, int states);
 void launch_step_gen(int k, const Rule& rule, const BoardEdges& place, bool bounded, i64 tile_cols, const u64* src, u64* dst,
                      i64 plane_stride, i64 board_words, const LaneDesc* plan, i64 n_waves, const StepParams& p, hipStream_t s);
+// step_ltl<R, BOUNDED, MASK> (ltl_kernel.hip): one generation of a Larger than Life rule (rule.range = R in 1 .. 7, the
+// box neighbourhood).  The plan is that of a pass of depth R (the generation's dependency cone: build_plan and
+// validate_plan with k = R), p.R >= R, p.h >= 2R + 1 and STEP_WRAP_Y (one rank: rows are read modulo h; a bounded board
+// masks the rows that wrap).  For the same plan it reads and writes no row or word step_temporal<R> would not: the
+// same words written, and no row read past a segment's last input row.  `place` and `bounded` as launch_step_envelope.
+int ltl_blocks_per_cu(int range, bool bounded);
+void launch_step_ltl(const Rule& rule, const BoardEdges& place, bool bounded, const u64* src, u64* dst, const LaneDesc* plan,
+                     i64 n_waves, const StepParams& p, hipStream_t s);
 // Generations rules (aux_kernels.hip).  state_counts: the tile's own cells in state s, s = 0 .. C - 1, added to the kCensusStripes
 // partial sums of slot s of `out` (the census's layout: C slots of kCensusSlotWords words, zeroed by the caller).
 // settle_decay: every decay plane ANDed with the complement of the live plane over the tile's own words.

@@ -402,6 +402,37 @@ PYBIND11_MODULE(_gol, m) {
             throw py::value_error(e.what());
         }
     });
+    // rule string -> (R, M, smin, smax, bmin, bmax) of a Larger than Life rule R<r>,C<c>,M<m>,S<a>..<b>,B<a>..<b>[,NM]
+    // (or the alias bosco); None for a rule of another family; ValueError on a string Rule::parse refuses
+    m.def("parse_ltl_rule", [](const std::string& s) -> py::object {
+        try {
+            const Rule r = Rule::parse(s);
+            if (!r.ltl()) return py::none();
+            return py::make_tuple((unsigned)r.range, (unsigned)r.middle, (unsigned)r.smin, (unsigned)r.smax, (unsigned)r.bmin,
+                                  (unsigned)r.bmax);
+        } catch (const Error& e) {
+            throw py::value_error(e.what());
+        }
+    });
+    // the canonical form of a rule string (Rule::str())
+    m.def("canonical_rule", [](const std::string& s) {
+        try {
+            return Rule::parse(s).str();
+        } catch (const Error& e) {
+            throw py::value_error(e.what());
+        }
+    });
+    // an LtL rule's four thresholds on the box sum that includes the centre: (blo, bhi, slo, shi) (Rule::ltl_thresholds)
+    m.def("ltl_thresholds", [](const std::string& s) {
+        try {
+            const Rule r = Rule::parse(s);
+            if (!r.ltl()) throw Error("ltl_thresholds: rule " + r.str() + " is not a Larger than Life rule");
+            const Rule::LtlThresholds t = r.ltl_thresholds();
+            return py::make_tuple((unsigned)t.blo, (unsigned)t.bhi, (unsigned)t.slo, (unsigned)t.shi);
+        } catch (const Error& e) {
+            throw py::value_error(e.what());
+        }
+    });
 
     py::class_<Engine>(m, "Engine")
         .def_static(

@@ -286,8 +286,65 @@ void state_counts(const u64* buf, const Layout& L, i64 plane_stride, const Rule&
         }
 }
 
+namespace {
+
+// One generation of a Larger than Life rule (rule.hpp) on the tile's own cells, which are the whole board (one rank):
+// the cells unpacked into a frame of `range` more cells on every side (the torus: the board repeated; a bounded board:
+// zeros), its summed-area table, and per cell the box sum T INCLUDING the centre against the rule's four thresholds.
+// Rows [0, h) of dst are written whole (ghost words zero: the caller refreshes them as after any superstep).
+void ltl_generation(const u64* src, u64* dst, const Layout& L, const Rule& rule, bool dead) {
+    const i64 h = L.h, w = L.w, R = rule.range, fh = h + 2 * R, fw = w + 2 * R;
+    const Rule::LtlThresholds t = rule.ltl_thresholds();
+    std::vector<u8> cells((size_t)(h * w));
+    for (i64 r = 0; r < h; ++r)
+        for (i64 c = 0; c < w; ++c) cells[(size_t)(r * w + c)] = (u8)((src[L.index(r, c >> 6)] >> storage_bit(c)) & 1ull);
+    // sat[(r + 1) * (fw + 1) + (c + 1)]: the live cells of frame rows [0, r] x frame columns [0, c]
+    std::vector<i32> sat((size_t)((fh + 1) * (fw + 1)), 0);
+    for (i64 r = 0; r < fh; ++r) {
+        const i64 br = r - R;
+        i32 run = 0;
+        for (i64 c = 0; c < fw; ++c) {
+            const i64 bc = c - R;
+            const bool inside = br >= 0 && br < h && bc >= 0 && bc < w;
+            if (inside || !dead) run += cells[(size_t)(pmod(br, h) * w + pmod(bc, w))];
+            sat[(size_t)((r + 1) * (fw + 1) + c + 1)] = sat[(size_t)(r * (fw + 1) + c + 1)] + run;
+        }
+    }
+    const i64 side = 2 * R + 1;
+#pragma omp parallel for schedule(static) if (h * w > 65536)
+    for (i64 r = 0; r < h; ++r) {
+        u64* out = dst + L.index(r, -1);
+        std::memset(out, 0, (size_t)(L.nw + 2) * 8);
+        for (i64 c = 0; c < w; ++c) {
+            // the box around (r, c) is frame rows [r, r + side) x frame columns [c, c + side)
+            const i32 T = sat[(size_t)((r + side) * (fw + 1) + c + side)] - sat[(size_t)(r * (fw + 1) + c + side)] -
+                          sat[(size_t)((r + side) * (fw + 1) + c)] + sat[(size_t)(r * (fw + 1) + c)];
+            const bool alive = cells[(size_t)(r * w + c)] != 0;
+            const bool next = alive ? (T >= (i32)t.slo && T <= (i32)t.shi) : (T >= (i32)t.blo && T <= (i32)t.bhi);
+            if (next) out[1 + (c >> 6)] |= 1ull << storage_bit(c);
+        }
+    }
+}
+
+}  // namespace
+
 u64* superstep(u64* a, u64* b, const Layout& L, int k, const Rule& rule, const Edges& edges, u64* counts, u64* sigs,
                const FilmOut& film, const DensityOut& density, u64* envelope, i64 plane_stride) {
+    if (rule.ltl()) {
+        if (counts || sigs || film.frames || density.maps || envelope)
+            throw Error("superstep: the per-generation records and the envelope are not built for Larger than Life rules (" + rule.str() + ")");
+        if (k < 1) throw Error(strprintf("superstep depth %d below 1", k));
+        if (edges.row0 != 0 || edges.word0 != 0 || (edges.dead() && (edges.rows != L.h || edges.cols != L.w)))
+            throw Error("superstep: a Larger than Life rule (" + rule.str() + ") steps a tile that is the whole board (one rank)");
+        if (L.h < 2 * (i64)rule.range + 1 || L.w < 2 * (i64)rule.range + 1)
+            throw Error(strprintf("superstep: rule %s needs a board of at least %d x %d cells, not %lld x %lld", rule.str().c_str(),
+                                  2 * rule.range + 1, 2 * rule.range + 1, (long long)L.h, (long long)L.w));
+        for (int g = 0; g < k; ++g) {  // one generation at a time
+            ltl_generation(a, b, L, rule, edges.dead());
+            std::swap(a, b);
+        }
+        return a;
+    }
     if (k < 1 || k > L.R) throw Error(strprintf("superstep depth %d outside 1..%d", k, L.R));
     if (rule.generations()) {
         if (counts || sigs || film.frames || density.maps || envelope)

@@ -19,6 +19,8 @@ void SoupBatch::validate(const SoupConfig& c) {
         throw Error(strprintf("soups: n = %lld is outside 1 .. 2^20", (long long)c.n));
     if (c.rule.generations())
         throw Error("soups: rule " + c.rule.str() + " is a Generations rule; soup batches run two-state rules only in this version");
+    if (c.rule.ltl())
+        throw Error("soups: rule " + c.rule.str() + " is a Larger than Life rule; soup batches run radius-1 rules only in this version");
     if (c.rule.nbhd != Nbhd::Moore)
         throw Error("soups: rule " + c.rule.str() + " counts the " + nbhd_name(c.rule.nbhd) +
                     " neighbourhood; soup batches run Moore rules only");

@@ -44,7 +44,40 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
         if (cfg_.backend == "hip" && cfg_.kernel != "auto" && cfg_.kernel != "rule")
             refuse(("kernel '" + cfg_.kernel + "'").c_str(), "step_gen runs every pass (use kernel auto or rule)");
     }
-    if (!cfg_.rule.is_conway()) {
+    if (cfg_.rule.ltl()) {
+        // A Larger than Life rule is a mode of its own too: one rank, one generation per superstep and per pass, no
+        // in-kernel record.  (Checkpoints and the rank agreement need Rule::code(), which such a rule does not have.)
+        const Rule& r = cfg_.rule;
+        Rule::from_ltl(r.range, r.middle, r.smin, r.smax, r.bmin, r.bmax);  // (a rule set by its fields: parse's checks)
+        const std::string rs = r.str();
+        auto refuse = [&rs](const std::string& option, const char* why) {
+            throw Error(option + " with the Larger than Life rule " + rs + ": " + why);
+        };
+        if (g_.dec.P > 1)
+            throw Error(strprintf("the Larger than Life rule %s on %d ranks: Larger than Life rules run on one rank (the exchange of "
+                                  "halos of depth R is not built)", rs.c_str(), g_.dec.P));
+        if (cfg_.census) refuse("census", "the census kernel counts inside the radius-1 kernels");
+        if (cfg_.signature) refuse("signature", "the signature kernel hashes inside the radius-1 kernels");
+        if (cfg_.film.on) refuse("film", "the film kernel stores frames inside the radius-1 kernels");
+        if (cfg_.density_film.on) refuse("density_film", "the density kernel counts inside the radius-1 kernels");
+        if (cfg_.envelope) refuse("envelope", "the envelope kernel records inside the radius-1 kernels");
+        if (cfg_.compat) refuse("compat (GOL_COMPAT=reference)", "the reference has one rule, B3/S23");
+        if (cfg_.subtiles == 2) refuse("subtiles=2 (GOL_SUBTILES=2)", "the sub-tile halves run B3/S23 only");
+        if (cfg_.self_exchange) refuse("self_exchange (GOL_SELF_EXCHANGE)", "the exchange of halos of depth R is not built");
+        if (cfg_.force_split) refuse("force_split (GOL_FORCE_SPLIT)", "the split schedule is not built for a box of range R");
+        if (cfg_.backend == "hip" && cfg_.kernel != "auto" && cfg_.kernel != "rule")
+            refuse("kernel '" + cfg_.kernel + "'", "step_ltl runs every pass (use kernel auto or rule)");
+        if (cfg_.kernel_depth != 0 && cfg_.kernel_depth != 1)
+            refuse(strprintf("kernel_depth %d (GOL_KERNEL_DEPTH)", cfg_.kernel_depth), "a pass is one generation (auto or 1)");
+        if (cfg_.halo_depth > 1)
+            refuse(strprintf("halo_depth %d (GOL_HALO_DEPTH)", cfg_.halo_depth), "a superstep is one generation (auto or 1)");
+        const i64 side = 2 * (i64)r.range + 1;
+        if (g_.dec.H < side || g_.dec.W < side)
+            throw Error(strprintf("rule %s on a %lld x %lld board: the box of range %d needs a board of at least %lld x %lld cells, "
+                                  "so that no neighbour is counted twice", rs.c_str(), (long long)g_.dec.H, (long long)g_.dec.W,
+                                  (int)r.range, (long long)side, (long long)side));
+    }
+    if (!cfg_.rule.is_conway() && !cfg_.rule.ltl()) {
         const std::string rs = cfg_.rule.str();
         if (cfg_.compat) throw Error("GOL_COMPAT=reference with rule " + rs + ": the reference has one rule, B3/S23");
         if (cfg_.subtiles == 2) throw Error("two sub-tiles per rank (GOL_SUBTILES=2) run B3/S23 only, not rule " + rs);
@@ -166,13 +199,16 @@ Engine::Engine(const Geometry& g, const EngineConfig& c, std::shared_ptr<Transpo
     // 4096 x 32768 2.44 -> 2.36, 8192 x 65536 5.93 -> 5.85 us/gen; profiles/per_rank_tiles_self_exchange.txt)
     const int want = cfg_.halo_depth > 0 ? cfg_.halo_depth : (sub_tall || tall_strips ? 128 : (tall_tiles ? 56 : 32));
     int R = clamp_halo_depth(g_.dec, want);
+    // A Larger than Life generation of range r has the dependency cone of r Life generations: the layout's halo depth is
+    // r, so that slack rows and ghost words exist as for a pass of depth r; the superstep itself is one generation.
+    if (ltl()) R = clamp_halo_depth(g_.dec, (int)cfg_.rule.range);
     if (two_d()) R = std::min(R, 63);  // the column halo is one 64-cell word
     if (cfg_.compat) {
         if (two_d()) throw Error("GOL_COMPAT=reference supports 1-D row strips only");
         R = 1;
     }
     L_ = Layout(g_.h, g_.w, R);
-    stats_.depth = R;
+    stats_.depth = ltl() ? 1 : R;
     stats_.rule = cfg_.rule.str();
     stats_.states = (int)cfg_.rule.states;
     stats_.boundary = boundary_name(cfg_.boundary);
@@ -275,10 +311,10 @@ void Engine::init(const PatternSpec& p) {
     Armed armed(wd_.get());
     gen_ = 0;
     stats_ = EngineStats{};
-    stats_.depth = L_.R;
+    stats_.depth = ltl() ? 1 : L_.R;
     stats_.kernel = backend_name() == "cpu" ? "cpu" : cfg_.kernel;
     stats_.schedule = halo_items(L_.R).empty() ? "local" : "full";
-    stats_.kernel_depth = L_.R;
+    stats_.kernel_depth = ltl() ? 1 : L_.R;
     stats_.rule = cfg_.rule.str();
     stats_.states = (int)cfg_.rule.states;
     stats_.boundary = boundary_name(cfg_.boundary);
@@ -400,7 +436,7 @@ void Engine::run(u64 generations) {
     Armed armed(wd_.get());
     while (generations > 0) {
         maybe_inject_fault();
-        int k = cfg_.compat ? 1 : supported_depth((int)std::min<u64>((u64)superstep_depth(), generations));
+        int k = cfg_.compat || ltl() ? 1 : supported_depth((int)std::min<u64>((u64)superstep_depth(), generations));
         {
             trace::Range r("gol.superstep");
             do_superstep(k);
@@ -639,6 +675,12 @@ void Engine::need_generations(const char* what) const {
 void Engine::need_two_states(const char* what) const {
     if (generations())
         throw Error(std::string(what) + ": not built for Generations rules in this version (the rule is " + cfg_.rule.str() + ")");
+}
+
+void Engine::need_rule_code(const char* what) const {
+    if (ltl())
+        throw Error(std::string(what) + ": not built for Larger than Life rules in this version (the rule is " + cfg_.rule.str() +
+                    "): a checkpoint's header holds Rule::code(), which such a rule does not have");
 }
 
 namespace {

@@ -119,7 +119,7 @@ HipEngine::HipEngine(const Geometry& g, const EngineConfig& c, std::shared_ptr<T
     kdepth_ = K;
     tdepth_ = supported_kernel_depth(std::min(kernel_ == "pipe" ? 8 : K, hipk::max_step_depth()));
     if (R != L_.R) L_ = Layout(L_.h, L_.w, R);
-    stats_.depth = R;
+    stats_.depth = ltl() ? 1 : R;  // (a Larger than Life rule: R is the rule's range, the superstep one generation)
     // slack rows: the temporal kernel prefetches 3 (shallow passes: 6) rows past a segment's last input row
     // (a Generations rule: 1 + M such boards per buffer, the decay planes behind the live plane)
     planes_ = 1 + cfg_.rule.decay_planes();
@@ -594,7 +594,7 @@ void HipEngine::finish_init() {
     if (!split_ && !dual_ && kern_[0] == "pipe")
         stats_.kernel = strprintf("pipe@%d(%dx%d,%d/CU)", pipe_k_, pipe_cur_.nw - 1, pipe_cur_.l, pipe_cur_.wg);
     if (rule_) {
-        const std::string rk = strprintf(generations() ? "gen@%d" : cfg_.envelope ? "envelope@%d" : cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", kdepth_);
+        const std::string rk = strprintf(ltl() ? "ltl@%d" : generations() ? "gen@%d" : cfg_.envelope ? "envelope@%d" : cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", kdepth_);
         stats_.kernel = split_ ? rk + "+boundary:" + rk : rk;
     }
     if (res_) {
@@ -621,7 +621,7 @@ void HipEngine::finish_init() {
                 const PassKernel pk = pass_kernel(kind, ps[j]);
                 c += (j ? "+" : "") + (pk == PK_PIPE   ? strprintf("pipe@%d(%dx%d,%d/CU)", ps[j], g->nw - 1, g->l, g->wg)
                                        : pk == PK_TILE ? strprintf("tile@%d", ps[j])
-                                       : pk == PK_RULE ? strprintf(generations() ? "gen@%d" : cfg_.envelope ? "envelope@%d" : cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", ps[j])
+                                       : pk == PK_RULE ? strprintf(ltl() ? "ltl@%d" : generations() ? "gen@%d" : cfg_.envelope ? "envelope@%d" : cfg_.density_film.on ? "density@%d" : cfg_.film.on ? "film@%d" : cfg_.signature ? "sig@%d" : cfg_.census ? "census@%d" : "rule@%d", ps[j])
                                                        : strprintf("temporal@%d", ps[j]));
             }
             tn += strprintf("%scut%d=%s", tn.empty() ? "" : " ", k, c.c_str());
@@ -887,7 +887,9 @@ void HipEngine::launch(int kind, int k, i64 e, const u64* src, u64* dst, hipStre
             pipe_used_ = true;
         } else if (pk == PK_RULE) {
             const hipk::BoardEdges edges{g_.row0, g_.dec.H, g_.word0(), g_.dec.W};
-            if (generations()) {  // (src and dst are live planes of boards allocated here: plane_words_ apart)
+            if (ltl()) {  // (k is 1; the plan is that of a pass of depth R: plan_depth)
+                hipk::launch_step_ltl(cfg_.rule, edges, dead_edges(), src, dst, p.d, p.waves, sp, s);
+            } else if (generations()) {  // (src and dst are live planes of boards allocated here: plane_words_ apart)
                 hipk::launch_step_gen(k, cfg_.rule, edges, dead_edges(), L_.w, src, dst, plane_words_, plane_words_, p.d, p.waves, sp, s);
             } else if (cfg_.envelope) {
                 hipk::launch_step_envelope(k, cfg_.rule, edges, dead_edges(), L_.w, src, dst, env_at_, p.d, p.waves, sp, s);

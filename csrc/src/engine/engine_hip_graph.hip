@@ -8,7 +8,7 @@ namespace hipeng {
 bool HipEngine::graph_shape(int& k, int& m) {
     if (!cfg_.graph || cfg_.profile) return false;
     // Census passes are not captured: the slot a pass counts into moves with every pass of a run.
-    if (recording() || generations()) return false;  // (signature mode too; Generations rules: eager launches)
+    if (recording() || generations() || ltl()) return false;  // (signature mode too; Generations and LtL rules: eager launches)
     // Sub-tile supersteps are not captured as a whole: captured with their fork/join across two
     // streams they replayed slower than eager launches on MI355X / ROCm 7.2 (32768^2: 14.2 vs
     // 12.8 us/gen over 20 generations, 13.0 vs 10.4 over 256; profiles/short_run_probe.txt).

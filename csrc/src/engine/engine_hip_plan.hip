@@ -99,7 +99,8 @@ std::vector<Region> HipEngine::regions(int kind, int k, i64 rem) const {
     return r;
 }
 
-const DevPlan& HipEngine::plan(int kind, int k, i64 e) {
+const DevPlan& HipEngine::plan(int kind, int k_pass, i64 e) {
+    const int k = plan_depth(k_pass);  // (a Larger than Life pass: the rule's range)
     // plans depend on e only through regions(): rows beyond the tile when y has neighbours,
     // ghost words when x has neighbours (so one plan serves every e of a local rank)
     const i64 ek = self_y() ? (self_x() ? 0 : (e > 0 ? 1 : 0)) : e;
@@ -178,7 +179,7 @@ const DevPlan& HipEngine::plan(int kind, int k, i64 e) {
             i64 bpc = blocks_per_cu(k, step_flags());
             // 256-thread blocks per CU = waves per SIMD; the tuned cap applies to the tuned depth
             // only (shallower passes are memory bound and want every resident wave)
-            if (occ_ > 0 && k == kdepth_) bpc = std::min<i64>(bpc, occ_);
+            if (occ_ > 0 && k_pass == kdepth_) bpc = std::min<i64>(bpc, occ_);
             const i64 resident = bpc * kWavesPerBlock * cus_;
             // big tiles: several rounds of segments near round_rows() rows (plan.hpp round_balanced_rows)
             rows = round_balanced_rows(rg, L_.nw, L_.h, k, resident, 2 * (i64)k, xwrap_by_plan(), round_rows(k));

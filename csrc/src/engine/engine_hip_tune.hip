@@ -173,7 +173,7 @@ void HipEngine::choose_schedule() {
         if (cfg_.sched == "auto" && split_used()) cands.push_back("split");
         // the one-tile superstep with its RCCL group captured in a graph (one replay per run)
         if (nbrs && device_transport_ && t_->graph_capturable() && cfg_.graph && !cfg_.profile && !cfg_.compat &&
-            cfg_.graph_rccl < 0 && !recording() && !generations())  // (census and signature runs are eager: graph_shape)
+            cfg_.graph_rccl < 0 && !recording() && !generations() && !ltl())  // (census and signature runs are eager: graph_shape)
             cands.push_back("full+graph");
     }
     graph_rccl_on_ = cfg_.graph_rccl == 1;
@@ -441,7 +441,7 @@ void HipEngine::time_schedule(const std::string& c, int k, int reps, bool eager)
     // candidate): `reps` supersteps captured once per candidate (round 0's warm-up call,
     // after one eager superstep that loads every kernel variant), one replay per call.
     const bool graphed = !eager && (c == "full+graph" ||
-                                    (c == "local" && cfg_.graph && !cfg_.profile && !cfg_.compat && graph_ok_ && !recording() && !generations()));
+                                    (c == "local" && cfg_.graph && !cfg_.profile && !cfg_.compat && graph_ok_ && !recording() && !generations() && !ltl()));
     if (graphed) {
         const std::string base = c == "local" ? "local" : "full";
         SchedGraph& sg = sched_graphs_[c];

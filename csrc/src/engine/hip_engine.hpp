@@ -281,6 +281,7 @@ class HipEngine : public Engine {
     // of 24 in 32-generation supersteps ran 24 + 8, and an 8-generation tile pass is 27% slower per
     // generation).  With neighbours every rank keeps R: the exchanges must match.
     int superstep_depth() const override {
+        if (ltl()) return 1;  // (a Larger than Life superstep is one generation; L_.R is the rule's range)
         if (res_) return std::max(L_.R, res_run_depth());
         if (dual_ || !tuned_ || cfg_.compat || kdepth_ <= 0 || kdepth_ >= L_.R || !halo_items(L_.R).empty())
             return L_.R;
@@ -322,7 +323,9 @@ class HipEngine : public Engine {
     // The streaming kernel of this engine: step_rule under a rule (rule_), else step_temporal.
     // (in census mode step_census, at its own depths, on either boundary)
     // (under a Generations rule step_gen, at the depths of its plane count)
+    // (under a Larger than Life rule step_ltl: one generation per pass, planned as a pass of depth R, plan_depth)
     bool depth_ok(int k) const {
+        if (ltl()) return k == 1;
         if (generations()) return k >= 1 && k <= hipk::max_generations_depth(states());
         if (cfg_.envelope) return k >= 1 && k <= hipk::max_envelope_depth(cfg_.rule.nbhd);
         if (cfg_.density_film.on) return k >= 1 && k <= hipk::max_density_depth(cfg_.rule.nbhd);
@@ -332,6 +335,7 @@ class HipEngine : public Engine {
         return rule_ ? hipk::rule_depth_supported(k, cfg_.rule.nbhd) : hipk::step_depth_supported(k);
     }
     int max_depth() const {
+        if (ltl()) return 1;
         if (generations()) return hipk::max_generations_depth(states());
         if (cfg_.envelope) return hipk::max_envelope_depth(cfg_.rule.nbhd);
         if (cfg_.density_film.on) return hipk::max_density_depth(cfg_.rule.nbhd);
@@ -341,6 +345,7 @@ class HipEngine : public Engine {
         return rule_ ? hipk::max_rule_depth(cfg_.rule.nbhd) : hipk::max_step_depth();
     }
     int blocks_per_cu(int k, u32 flags) const {
+        if (ltl()) return hipk::ltl_blocks_per_cu((int)cfg_.rule.range, dead_edges());
         if (generations()) return hipk::generations_blocks_per_cu(k, flags, dead_edges(), states());
         if (cfg_.envelope) return hipk::envelope_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
         if (cfg_.density_film.on) return hipk::density_blocks_per_cu(k, flags, dead_edges(), cfg_.rule.nbhd);
@@ -350,6 +355,10 @@ class HipEngine : public Engine {
         if (dead_edges()) return hipk::rule_bounded_blocks_per_cu(k, flags, cfg_.rule.nbhd);
         return rule_ ? hipk::rule_blocks_per_cu(k, flags, cfg_.rule.nbhd) : hipk::step_blocks_per_cu(k, flags);
     }
+    // The depth a pass of k generations is planned, validated and allocated at: a Larger than Life generation of range R
+    // has the dependency cone of R Life generations (R rows up and down, R cells left and right), so its pass is a pass
+    // of depth R for build_plan, validate_plan, the halo lanes and the slack rows.
+    int plan_depth(int k) const { return ltl() ? (int)cfg_.rule.range : k; }
     int supported_kernel_depth(int want) const {
         while (want > 1 && !depth_ok(want)) --want;
         return std::max(1, want);

@@ -311,6 +311,7 @@ void pread_all(int fd, void* buf, size_t n, off_t off, const std::string& name) 
 
 void save_checkpoint(Engine& eng, const std::string& prefix, u64 seed) {
     eng.need_two_states("save_checkpoint()");
+    eng.need_rule_code("save_checkpoint()");
     trace::Range range("gol.checkpoint");
     const Geometry& g = eng.geometry();
     Transport& t = eng.transport();
@@ -371,6 +372,7 @@ void save_checkpoint(Engine& eng, const std::string& prefix, u64 seed) {
 
 u64 load_checkpoint(Engine& eng, const std::string& prefix) {
     eng.need_two_states("load_checkpoint()");
+    eng.need_rule_code("load_checkpoint()");
     const Geometry& g = eng.geometry();
     const std::string name = ckpt_name(prefix);
     const int fd = open(name.c_str(), O_RDONLY);
@@ -656,6 +658,9 @@ int run_rank(const CliArgs& a, const Options& o, const CliPattern& cp, const Lau
                 throw Error("checkpoints (GOL_RESTART, GOL_CHECKPOINT_EVERY) are not built for Generations rules in this version (the rule is " +
                             rs + ")");
         }
+        if (ec.rule.ltl() && (!o.restart.empty() || o.checkpoint_every > 0))
+            throw Error("checkpoints (GOL_RESTART, GOL_CHECKPOINT_EVERY) are not built for Larger than Life rules in this version (the rule is " +
+                        ec.rule.str() + ")");
         ec.run_hint = o.checkpoint_every > 0 ? (u64)o.checkpoint_every : (u64)a.iterations;
         std::unique_ptr<Engine> eng = Engine::create(g, ec, t);
         if (o.verbose && rank == 0) fprintf(stderr, "[gol] %s\n", eng->describe().c_str());

@@ -64,6 +64,15 @@ class Simulation:
                   ``max_generations_depth(C)`` generations).  One rank, Moore, no recording mode, ``compat``,
                   ``subtiles=2``, ``self_exchange``, ``force_split`` or specialised kernel; checkpoints, ``save_rle``,
                   dumps and the tensor calls are refused in this version.
+                  ``"R5,C0,M1,S34..58,B34..45,NM"`` (or the alias ``"bosco"``) is a Larger than Life rule: two states, the
+                  (2R+1) x (2R+1) box around a cell with R from 1 to 7, the cell itself counted iff M is 1, birth and
+                  survival by count intervals (``ops.numpy_ltl`` is the definition, ``ops.parse_ltl_rule`` the parser;
+                  :attr:`ltl` holds ``(R, M, smin, smax, bmin, bmax)``, ``None`` for every other rule).  The board is
+                  the ordinary two-state board: every reader and writer works.  HIP: ``step_ltl`` runs one generation
+                  per pass (``stats()["kernel"]`` is ``ltl@1``, eager launches).  One rank, a board of at least
+                  2R + 1 cells either way, no recording mode, ``compat``, ``subtiles=2``, ``self_exchange``,
+                  ``force_split``, specialised kernel or ``kernel_depth`` / ``halo_depth`` above 1; checkpoints,
+                  ``SoupBatch`` and ``ops.evolve`` refuse such a rule in this version.
     kernel_depth: generations per kernel pass (HIP; 0 = auto).  A superstep of halo_depth
                   generations runs as several kernel passes in 1-D (communication-avoiding halos).
     kernel:       HIP stencil kernel: ``"auto"`` (candidates timed at init), ``"temporal"``,
@@ -350,6 +359,42 @@ class Simulation:
                     f"the Generations kernel's deepest pass with {self.states} states is "
                     f"{_gol.max_generations_depth(self.states)} generations",
                 )
+        self.ltl = _gol.parse_ltl_rule(cfg.rule)  # (R, M, smin, smax, bmin, bmax) of a Larger than Life rule, else None
+        if self.ltl is not None:  # what this version does not run with such a rule, each named
+            r = cfg.rule
+
+            def refuse_ltl(option: str, why: str):
+                raise ValueError(f"{option} with the Larger than Life rule {r}: {why}")
+
+            if P > 1:
+                raise ValueError(f"the Larger than Life rule {r} on {P} ranks: Larger than Life rules run on one rank")
+            if cfg.census:
+                refuse_ltl("census=True", "the census kernel counts inside the radius-1 kernels")
+            if cfg.signature:
+                refuse_ltl("signature=True", "the signature kernel hashes inside the radius-1 kernels")
+            if cfg.film is not None:
+                refuse_ltl("film", "the film kernel stores frames inside the radius-1 kernels")
+            if cfg.density_film is not None:
+                refuse_ltl("density_film", "the density kernel counts inside the radius-1 kernels")
+            if envelope:
+                refuse_ltl("envelope=True", "the envelope kernel records inside the radius-1 kernels")
+            if bool(self_exchange):
+                refuse_ltl("self_exchange=True", "the exchange of halos of depth R is not built")
+            if bool(force_split):
+                refuse_ltl("force_split=True", "the split schedule is not built for a box of range R")
+            if self.backend == "hip" and kernel not in ("auto", "rule"):
+                refuse_ltl(f"kernel {kernel!r}", "step_ltl runs every pass (use auto or rule)")
+            if int(kernel_depth) not in (0, 1):
+                refuse_ltl(f"kernel_depth {kernel_depth}", "a pass is one generation (auto or 1)")
+            if int(halo_depth) not in (0, 1):
+                refuse_ltl(f"halo_depth {halo_depth}", "a superstep is one generation (auto or 1)")
+            side = 2 * self.ltl[0] + 1
+            H, W = self.decomposition.H, self.decomposition.W
+            if H < side or W < side:
+                raise ValueError(
+                    f"rule {r} on a {H} x {W} board: the box of range {self.ltl[0]} needs a board of at least {side} x {side} "
+                    "cells, so that no neighbour is counted twice"
+                )
         cfg.envelope = bool(envelope)
         cfg.subtiles = int(subtiles)  # 2 / 0 / -1 auto: two sub-tiles per rank on two streams (HIP, 1-D)
         cfg.run_hint = int(run_hint)  # generations of the runs to come: one replay graph covers them
@@ -431,6 +476,13 @@ class Simulation:
         if self.states <= 2:
             raise ValueError(f"state_counts() needs a Generations rule (B<digits>/S<digits>/C<n>); rule {self.config.rule} has two states")
         return self.engine.state_counts()
+
+    def _no_ltl(self, what: str) -> None:
+        if self.ltl is not None:
+            raise ValueError(
+                f"{what} is not built for Larger than Life rules in this version (the rule is {self.config.rule}): "
+                "a checkpoint's header holds the rule's code, which such a rule does not have"
+            )
 
     def _two_states(self, what: str) -> None:
         if self.states > 2:
@@ -904,9 +956,11 @@ class Simulation:
         grid with the same global board size.
         """
         self._two_states("checkpoint()")
+        self._no_ltl("checkpoint()")
         _gol.save_checkpoint(self.engine, prefix, self.pattern.seed if self.pattern else 0)
 
     def restore(self, prefix: str) -> int:
         """Load this rank's rectangle of ``<prefix>.gol``; returns the snapshot's generation."""
         self._two_states("restore()")
+        self._no_ltl("restore()")
         return int(_gol.load_checkpoint(self.engine, prefix))

@@ -8,6 +8,7 @@ from .oracle import (  # noqa: F401
     numpy_envelope,
     numpy_film,
     numpy_generations,
+    numpy_ltl,
     numpy_signature,
     numpy_signatures,
     numpy_soup_settle,
@@ -15,6 +16,9 @@ from .oracle import (  # noqa: F401
     numpy_step_rule,
     numpy_step_rule_bounded,
     parse_generations_rule,
+    is_ltl_rule,
+    ltl_rule_string,
+    parse_ltl_rule,
     parse_rule,
     parse_rule_nbhd,
     parse_rule_states,

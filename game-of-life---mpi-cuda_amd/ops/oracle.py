@@ -196,10 +196,140 @@ def parse_generations_rule(rule) -> tuple:
 def parse_rule_states(rule) -> int:
     """The states of a rule string: 2 for a life-like rule (any neighbourhood), C for a Generations rule
     ``B<digits>/S<digits>/C<n>``."""
+    if is_ltl_rule(rule):
+        parse_ltl_rule(rule)
+        return 2
     if isinstance(rule, str) and rule.count("/") < 2:
         parse_rule_nbhd(rule)
         return 2
     return parse_generations_rule(rule)[2]
+
+
+_B0_TEXT = "B0 rules are out of scope (the dead background would come alive)"
+LTL_MAX_RANGE = 7  # counts of up to (2 * 7 + 1) ** 2 = 225 fit 8 bit planes
+
+
+def is_ltl_rule(rule) -> bool:
+    """Whether a rule string names the Larger than Life family: the alias ``bosco``, or a string that begins with the
+    ``R`` field (``replicator`` is a life-like alias).  Says nothing about validity."""
+    if not isinstance(rule, str):
+        return False
+    low = rule.lower()
+    return low == "bosco" or (len(low) >= 2 and low[0] == "r" and low != "replicator")
+
+
+def _ltl_number(rule, text: str, what: str) -> int:
+    if not text or not text.isascii() or not text.isdigit():
+        raise ValueError(f"invalid rule {rule!r}: {text!r} in {what} is not a number")
+    if len(text) > 1 and text[0] == "0":
+        raise ValueError(f"invalid rule {rule!r}: {text!r} in {what} has a leading zero")
+    if len(text) > 4:
+        raise ValueError(f"invalid rule {rule!r}: {text!r} in {what} is out of range")
+    return int(text)
+
+
+def parse_ltl_rule(rule) -> tuple:
+    """A Larger than Life rule as ``(R, M, smin, smax, bmin, bmax)``: Golly's
+    ``R<r>,C<c>,M<m>,S<smin>..<smax>,B<bmin>..<bmax>[,N<n>]`` (letters in either case, the fields in this order) or the
+    alias ``bosco`` (``R5,C0,M1,S34..58,B34..45,NM``), or such a 6-tuple.  ``r`` runs from 1 to 7, ``c`` is 0 or 2 (two
+    states; history states are not built), ``m`` 0 or 1, ``n`` is ``M`` (the box; ``NN`` and ``NC`` are not built) or
+    missing; intervals need ``min <= max <= (2r+1)**2`` and ``bmin >= 1`` (B0).  Refused as well: a field twice or
+    missing, spaces, leading zeros, a trailing comma.  A parser of its own, independent of the native one."""
+    if not isinstance(rule, str):
+        r, m, smin, smax, bmin, bmax = (int(v) for v in rule)
+        c = 0
+    else:
+        text = rule.lower()
+        if text == "bosco":
+            text = "r5,c0,m1,s34..58,b34..45,nm"
+        if not is_ltl_rule(text):
+            raise ValueError(f"invalid rule {rule!r}: not a Larger than Life rule (R<r>,C<c>,M<m>,S<a>..<b>,B<a>..<b>[,NM])")
+        if any(ch.isspace() for ch in text):
+            raise ValueError(f"invalid rule {rule!r}: spaces in a Larger than Life rule")
+        if text.endswith(","):
+            raise ValueError(f"invalid rule {rule!r}: a trailing comma")
+        seen = {}
+        for field in text.split(","):
+            letter, rest = field[:1], field[1:]
+            if letter == "" or letter not in "rcmsbn":
+                raise ValueError(f"invalid rule {rule!r}: unknown field {field!r} (the fields are R, C, M, S, B and N)")
+            if letter in seen:
+                raise ValueError(f"invalid rule {rule!r}: field {letter.upper()} twice")
+            if letter == "n":
+                if rest in ("n", "c"):
+                    name = "NN, the von Neumann" if rest == "n" else "NC, the circular"
+                    raise ValueError(f"invalid rule {rule!r}: {name} neighbourhood of range R, is not built; NM (the box) only")
+                if rest != "m":
+                    raise ValueError(f"invalid rule {rule!r}: neighbourhood {field!r}: NM (the box) only")
+                seen[letter] = "m"
+            elif letter in "sb":
+                lo, dots, hi = rest.partition("..")
+                if not dots:
+                    raise ValueError(f"invalid rule {rule!r}: field {field!r} is not {letter.upper()}<min>..<max>")
+                what = f"{letter.upper()}<min>..<max>"
+                seen[letter] = (_ltl_number(rule, lo, what), _ltl_number(rule, hi, what))
+            else:
+                seen[letter] = _ltl_number(rule, rest, f"{letter.upper()}<n>")
+        for letter in "rcmsb":
+            if letter not in seen:
+                raise ValueError(f"invalid rule {rule!r}: field {letter.upper()} is missing")
+        if "".join(seen) not in ("rcmsb", "rcmsbn"):
+            raise ValueError(f"invalid rule {rule!r}: the fields come in the order R,C,M,S,B[,N]")
+        r, c, m = seen["r"], seen["c"], seen["m"]
+        (smin, smax), (bmin, bmax) = seen["s"], seen["b"]
+    if not 1 <= r <= LTL_MAX_RANGE:
+        raise ValueError(f"invalid rule {rule!r}: range R{r}: Larger than Life rules run with R1 to R{LTL_MAX_RANGE}")
+    if c >= 3:
+        raise ValueError(f"invalid rule {rule!r}: C{c}: Larger than Life rules with history states (C >= 3) are not built")
+    if c == 1:
+        raise ValueError(f"invalid rule {rule!r}: C1: the state count is C0 or C2 (two states)")
+    if m not in (0, 1):
+        raise ValueError(f"invalid rule {rule!r}: M{m}: the middle flag is M0 or M1")
+    box = (2 * r + 1) ** 2
+    for name, lo, hi in (("S", smin, smax), ("B", bmin, bmax)):
+        if not 0 <= lo <= hi <= box:
+            raise ValueError(f"invalid rule {rule!r}: {name}{lo}..{hi}: an interval needs min <= max <= (2*{r}+1)^2 = {box}")
+    if bmin == 0:
+        raise ValueError(f"invalid rule {rule!r}: {_B0_TEXT}")
+    return r, m, smin, smax, bmin, bmax
+
+
+def ltl_rule_string(rule) -> str:
+    """Canonical ``R<r>,C0,M<m>,S<smin>..<smax>,B<bmin>..<bmax>,NM``: always all six fields, with ``C0``."""
+    r, m, smin, smax, bmin, bmax = parse_ltl_rule(rule)
+    return f"R{r},C0,M{m},S{smin}..{smax},B{bmin}..{bmax},NM"
+
+
+def numpy_ltl(board: np.ndarray, rule, gens: int, boundary: str = "torus") -> np.ndarray:
+    """The oracle of the Larger than Life rules: ``gens`` generations of the 0/1 array ``board`` under ``rule`` (a string
+    or ``(R, M, smin, smax, bmin, bmax)``), Golly's semantics.  ``n`` is the number of live cells in the
+    ``(2R+1) x (2R+1)`` box around a cell, the cell itself counted iff M is 1; a dead cell is born iff
+    ``bmin <= n <= bmax``, a live cell survives iff ``smin <= n <= smax``.  Plain numpy: summed rolls on the torus
+    (``boundary="torus"``), a zero pad on a bounded board (``"dead"``)."""
+    R, M, smin, smax, bmin, bmax = parse_ltl_rule(rule)
+    if boundary not in ("torus", "dead"):
+        raise ValueError(f"boundary must be torus or dead, got {boundary!r}")
+    b = np.asarray(board, dtype=np.uint8)
+    if b.ndim != 2:
+        raise ValueError(f"a board is a 2-D array, got shape {b.shape}")
+    H, W = b.shape
+    if H < 2 * R + 1 or W < 2 * R + 1:
+        raise ValueError(f"a {H} x {W} board is smaller than the {2 * R + 1} x {2 * R + 1} box of range {R}")
+    for _ in range(int(gens)):
+        live = b.astype(np.int32)
+        if boundary == "torus":
+            cols = sum(np.roll(live, dx, axis=1) for dx in range(-R, R + 1))
+            n = sum(np.roll(cols, dy, axis=0) for dy in range(-R, R + 1))
+        else:
+            pad = np.zeros((H + 2 * R, W + 2 * R), dtype=np.int32)
+            pad[R : R + H, R : R + W] = live
+            cols = sum(pad[:, dx : dx + W] for dx in range(2 * R + 1))
+            n = sum(cols[dy : dy + H, :] for dy in range(2 * R + 1))
+        if not M:
+            n = n - live
+        alive = b == 1
+        b = np.where(alive, (n >= smin) & (n <= smax), (n >= bmin) & (n <= bmax)).astype(np.uint8)
+    return b
 
 
 def numpy_generations(board: np.ndarray, rule, gens: int, boundary: str = "torus") -> np.ndarray:

@@ -15,9 +15,9 @@ def pattern_from_cells(cells, rule: str = "", topology: str = "", bound_cols: in
     if cells.ndim != 2 or cells.shape[0] < 1 or cells.shape[1] < 1:
         raise ValueError(f"a pattern is a 2-D array with at least one cell, got shape {cells.shape}")
     if rule:
-        from .oracle import rule_string
+        from .oracle import is_ltl_rule, ltl_rule_string, rule_string
 
-        rule = rule_string(rule)
+        rule = ltl_rule_string(rule) if is_ltl_rule(rule) else rule_string(rule)
     return _gol.RlePattern(pack_cells(cells != 0), int(cells.shape[1]), rule, topology, int(bound_cols), int(bound_rows))
 
 
