@@ -323,8 +323,9 @@ N_RANDOM_SOUPS = 300
 
 
 def placed_soups():
-    """5 soups of 64^2 and 3 of 128^2 with blocks, blinkers, beehives and gliders across the row wrap 63 -> 0, the word
-    seam 63 | 64 of a 128^2 soup, and the corner."""
+    """5 soups of 64^2, 3 of 128^2 and 3 of 256^2 with blocks, blinkers, beehives and gliders across the row wrap S - 1 -> 0,
+    the column wrap, the word seam 63 | 64 of a 128^2 soup, the word seams 127 | 128 and 191 | 192 of a 256^2 soup (k_match
+    with nw = pitch = 4), and the corner."""
     def soups(S, n):
         b = np.zeros((n, S, S), dtype=np.uint8)
         stamp_wrapped(b[0], BLOCK, S - 1, 10)               # across the row wrap
@@ -342,12 +343,23 @@ def placed_soups():
             stamp_wrapped(b[1], BLINKER, 70, 62)
             stamp_wrapped(b[2], BEEHIVE, 90, 62)
             stamp_wrapped(b[2], turned(GLIDER_CELLS, 5), 60, 62)
+        if S == 256:  # the four patterns across each of the word seams 127 | 128 and 191 | 192, one soup per seam
+            for i, seam in enumerate((128, 192)):
+                stamp_wrapped(b[i], BLOCK, 50, seam - 1)
+                stamp_wrapped(b[i], BLINKER, 70, seam - 2)
+                stamp_wrapped(b[i], BEEHIVE, 90, seam - 2)
+                stamp_wrapped(b[i], turned(GLIDER_CELLS, 5 + i), 60, seam - 2)
+                stamp_wrapped(b[i], turned(BEEHIVE, 1), 110, seam - 1)
+            stamp_wrapped(b[2], BLOCK, 127, 63)             # the crossing of the seams 63 | 64 and rows 127 | 128
+            stamp_wrapped(b[0], BLOCK, 150, 255)            # across the column wrap 255 | 0, beside the blinker at row 20
+            stamp_wrapped(b[0], GLIDER_CELLS, 200, 254)
+            stamp_wrapped(b[1], BEEHIVE, 150, 254)
         for k in range(3, n):
             stamp_wrapped(b[k], turned(GLIDER_CELLS, k), 5 * k, S - 3 + k)
             stamp_wrapped(b[k], BEEHIVE, S - 2, 7 * k)
         return b
 
-    return soups(64, 5), soups(128, 3)
+    return soups(64, 5), soups(128, 3), soups(256, 3)
 
 
 def oracle_counts(boards, orientations="all"):
@@ -369,6 +381,8 @@ def check_placed_soups(gol, backend):
             _soup_oracle[key] = oracle_counts(boards)
         want = _soup_oracle[key]
         assert want[0, 0] >= 1 and want[0, 1] >= 1 and want[0, 2] >= 1 and want[2, 3] >= 1 and want[1, 3] >= 1
+        if boards.shape[1] == 256:  # block, blinker, beehive, glider: the oracle finds every stamp of the two seam soups
+            assert list(want[0]) == [3, 2, 3, 2] and list(want[1]) == [2, 2, 3, 2]
         got = batch.match_counts(SOUP_PATTERNS)
         assert got.dtype == np.uint32 and got.shape == want.shape
         assert np.array_equal(got, want)

@@ -2,7 +2,9 @@
 
 The cases are soup_cases.py's, shared with test_gpu_soups.py: plain stepping bit for bit, seam patterns from arrays,
 random soups that settle (all four result arrays and the boards against the oracle), soups that do not, independence of
-the chunk and of resumption, mixed settling times in one batch.  Every comparison is exact."""
+the chunk and of resumption, mixed settling times in one batch; at 128^2 and 256^2 the sparse, placed and tiled boards
+that settle within the oracle's reach, so the m = 2 and m = 4 paths of soups_cpu.cpp (the GPU tests' second reference)
+are themselves checked against the oracle, and max_gens on the generation of the hit.  Every comparison is exact."""
 import os
 
 import numpy as np
@@ -48,9 +50,29 @@ def test_plain_steps_256(gol):
     sc.check_plain_steps(gol, BACKEND, 256, "B36/S23")
 
 
-@pytest.mark.parametrize("S", [64, 128])
+@pytest.mark.parametrize("S", sc.SIZES)
 def test_seam_patterns(gol, S):
     sc.check_patterns(gol, BACKEND, S)
+
+
+@pytest.mark.parametrize("rule", sc.FAMILY_RULES)
+@pytest.mark.parametrize("S", sc.SIZES)
+def test_three_families_settle(gol, S, rule):
+    """Sparse, placed and tiled boards in one batch: the m = 2 and m = 4 paths of soups_cpu.cpp against the oracle."""
+    sc.check_variant(gol, BACKEND, S, rule)
+
+
+@pytest.mark.parametrize("S,rule", sc.FAMILY_CHUNKS)
+def test_family_chunks_and_resumption(gol, S, rule):
+    sc.check_family_chunks(gol, BACKEND, S, rule)
+
+
+def test_mixed_settling_times_256(gol):
+    sc.check_mixed(gol, BACKEND, chunk=512, S=256)
+
+
+def test_max_gens_on_the_hit(gol):
+    sc.check_max_gens_edges(gol, BACKEND)
 
 
 @pytest.mark.parametrize("S,rule,n", sc.SETTLING)
