@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "gol/cells.hpp"
+#include "gol/components.hpp"
 #include "gol/density_film.hpp"
 #include "gol/film.hpp"
 #include "gol/geometry.hpp"
@@ -331,6 +332,15 @@ class Engine {
     MatchResult match(const std::vector<std::pair<int, MatchTemplate>>& ts, i64 max_hits, bool positions);
     // dst (h x w dense cells, as read_tile_cells takes them): 1 where any template of `ts` matches, else 0.
     void match_cells(const std::vector<std::pair<int, MatchTemplate>>& ts, const CellBuffer& dst);
+    // ----- connected components (gol/components.hpp) -----
+    // The objects of the current board (a Generations rule: of its live plane), torus or bounded as the engine runs.  One
+    // rank only, refused as match() refuses; max_objects < 1 and a board of 2^31 cells or more are refused too, all before
+    // anything is launched.  want_records = false returns the count alone.  HIP: the kernels of components_kernel.hip;
+    // only the counter and the records leave the device.
+    ComponentsResult components(CcNeighbourhood nb, i64 max_objects, bool hashes, bool want_records);
+    // dst: h x w labels (i32, or i64 with int64) in row-major order, in the backend's kind of memory as the dense cells
+    // are; numel must be h * w.
+    void components_labels(CcNeighbourhood nb, void* dst, bool int64, i64 numel);
 
     // ----- dense cells: the tensor readers and writers (gol/cells.hpp) -----
     // The caller's buffer is one element per cell (u8, f16, bf16 or f32; exact 0 and 1 out, != 0 alive in).  HIP
@@ -505,6 +515,10 @@ class Engine {
     virtual void match_positions_local(i64 cap, std::vector<i32>* out) = 0;
     virtual void match_bitmap_cells(const CellBuffer& dst) = 0;
     void check_match(const std::vector<std::pair<int, MatchTemplate>>& ts, const char* what) const;
+    // Connected components: the backends' parts, on the current board.
+    virtual ComponentsResult components_local(CcNeighbourhood nb, i64 max_objects, bool hashes, bool want_records) = 0;
+    virtual void components_labels_cells(CcNeighbourhood nb, void* dst, bool int64) = 0;
+    void check_components(i64 max_objects, const char* what) const;
 
     Geometry g_;
     EngineConfig cfg_;

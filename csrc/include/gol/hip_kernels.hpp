@@ -38,6 +38,8 @@
 //   reduce_board      — population + decomposition-invariant fingerprint.
 //   window_bytes / density / stamp — views of the live board and pattern stamping (view_kernels.hip).
 //   match / match_positions — template matching on the live board and on soup batches (match_kernel.hip).
+//   cc_init / cc_merge / cc_flatten / cc_roots / cc_stats / cc_hash / cc_labels — connected components of the live
+//                       board and of soup batches: a lock-free union-find over runs of ones (components_kernel.hip).
 //   naive_byte_step   — byte-per-cell, thread-per-cell yardstick of the reference's algorithm class
 //                       (no printf), used only by the benchmark for comparison.
 #pragma once
@@ -46,6 +48,7 @@
 
 #include <vector>
 
+#include "gol/components.hpp"
 #include "gol/density_film.hpp"
 #include "gol/geometry.hpp"
 #include "gol/match.hpp"
@@ -330,6 +333,38 @@ void launch_match(const u64* board, const MatchGeo& g, const MatchTemplate& t, u
 // k_match_positions: the set bits of board 0's bitmap as (row, col) pairs of i32 in no particular order: the first `cap`
 // to arrive are stored at out, and cursor[0] (zeroed by the caller) ends as the number of set bits.
 void launch_match_positions(const u64* bitmap, const MatchGeo& g, i32* out, i64 cap, u64* cursor, hipStream_t s);
+
+// ----- connected components (components_kernel.hip; gol/components.hpp) -----
+// The boards are addressed by a MatchGeo.  parent: cc_parent_bytes(g) = 4 bytes per cell of every board, uninitialised
+// (only the slots of run heads are used).  All launchers refuse batch * h * w >= 2^31.  The order of a call:
+//   launch_cc_init, launch_cc_merge                                     the forest of the runs;
+//   launch_cc_roots with rec = nullptr                                  count[0] (and per_board[b]) alone; or
+//   launch_cc_flatten, then launch_cc_labels                            the label tensor of one board; or
+//   launch_cc_flatten, launch_cc_roots, launch_cc_stats, launch_cc_hash the records: rec (cap CcRecords) and sums (cap x 8
+//                                                                       u64, nullptr: no hashes) need no clearing, the
+//                                                                       counters do.
+// Objects beyond the first cap to draw an id are counted and get no record.  wave_reduce = false leaves out the
+// reduction across a wave whose words all lie in one object (a measurement switch; the results are the same).
+size_t cc_parent_bytes(const MatchGeo& g);
+void launch_cc_init(const u64* board, const MatchGeo& g, i32* parent, hipStream_t s);
+void launch_cc_merge(const u64* board, const MatchGeo& g, CcNeighbourhood nb, i32* parent, hipStream_t s);
+void launch_cc_flatten(const u64* board, const MatchGeo& g, i32* parent, hipStream_t s);
+void launch_cc_roots(const u64* board, const MatchGeo& g, i32* parent, u32* count, u32* per_board, CcRecord* rec, u64* sums,
+                     i64 cap, hipStream_t s);
+void launch_cc_stats(const u64* board, const MatchGeo& g, const i32* parent, CcRecord* rec, i64 cap, bool wave_reduce, hipStream_t s);
+void launch_cc_hash(const u64* board, const MatchGeo& g, const i32* parent, const CcRecord* rec, u64* sums, i64 cap,
+                    bool wave_reduce, hipStream_t s);
+// (h, w) labels of board 0 in row-major order, i32 or i64 elements (16-byte stores where w % 4 == 0 and out is aligned)
+void launch_cc_labels(const u64* board, const MatchGeo& g, const i32* parent, void* out, bool int64, hipStream_t s);
+// The whole records call on one stream, shared by the engine and the soup batches: scratch is allocated here and freed
+// before the return (see docs/PERFORMANCE.md, section 33), and only the counters and the records leave the device.
+ComponentsResult run_components(const u64* board, const MatchGeo& g, CcNeighbourhood nb, i64 max_objects, bool hashes,
+                                bool want_records, hipStream_t s);
+// The label call (init, merge, flatten, labels) with the same scratch handling; synchronises s before it returns.
+void run_component_labels(const u64* board, const MatchGeo& g, CcNeighbourhood nb, void* out, bool int64, hipStream_t s);
+// Measurement switch for tools/measure_components.py: whether run_components() lets k_cc_stats and k_cc_hash reduce
+// across a wave (the default).  Process-wide; the results do not depend on it.
+void cc_set_wave_reduce(bool on);
 
 // Yardstick: one byte per cell, one thread per cell, x-wrap + two ghost rows (reference class).
 void launch_naive_byte_step(const u8* src, u8* dst, i64 w, i64 h, const u8* above, const u8* below, int threads,

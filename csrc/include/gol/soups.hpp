@@ -26,6 +26,7 @@
 
 #include "gol/cells.hpp"
 #include "gol/common.hpp"
+#include "gol/components.hpp"
 #include "gol/match.hpp"
 #include "gol/rule.hpp"
 
@@ -115,6 +116,11 @@ class SoupBatch {
     // runs.  HIP: the batch's stream is synchronised first (a pending step() is included), then one k_match launch per
     // oriented template over all soups adds into one counter per soup; no bitmap is kept.
     std::vector<u32> match_counts(const std::vector<std::vector<MatchTemplate>>& templates);
+    // Connected components (gol/components.hpp) of every soup's current board, each its own torus: the records carry the
+    // soup's index, anchors and boxes are in the soup's own coordinates, per_board holds the objects of every soup.
+    // max_objects < 1 and n * S * S >= 2^31 are refused before anything runs.  HIP: the batch's stream is synchronised
+    // first (a pending step() is included), then the kernels of components_kernel.hip run over the whole store.
+    ComponentsResult components(CcNeighbourhood nb, i64 max_objects, bool hashes, bool want_records);
     SoupStats stats() const;
     // Waits for the launches of step() (HIP; every other call returns finished work).
     virtual void synchronize() {}
@@ -135,6 +141,7 @@ class SoupBatch {
     virtual void do_init_cells(const CellBuffer& src) = 0;  // the boards and, as do_upload, the states
     // counts[i] = the matches of the templates, summed, on soup i's board (n counts)
     virtual void do_match_counts(const std::vector<MatchTemplate>& oriented, u32* counts) = 0;
+    virtual ComponentsResult do_components(CcNeighbourhood nb, i64 max_objects, bool hashes, bool want_records) = 0;
     // the soups first .. first + count - 1 of a store of n x S x m words
     CellSource soup_source(const u64* store, i64 first, i64 count) const;
     CellTarget soup_target(u64* store) const;

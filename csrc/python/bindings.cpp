@@ -156,6 +156,24 @@ py::array_t<u8> template_cells(const MatchTemplate& t, bool care) {
     return a;
 }
 
+// ComponentsResult as (count, board (k,), anchor (k, 2), population (k,), bbox (k, 4), hash (k,) or empty, truncated,
+// per_board)
+py::tuple components_tuple(const ComponentsResult& r) {
+    const py::ssize_t k = (py::ssize_t)r.population.size();
+    py::array_t<i64> board(k), anchor({k, (py::ssize_t)2}), bbox({k, (py::ssize_t)4});
+    py::array_t<u32> pop(k), per((py::ssize_t)r.per_board.size());
+    py::array_t<u64> hash((py::ssize_t)r.hash.size());
+    if (k) {
+        std::memcpy(board.mutable_data(), r.board.data(), (size_t)k * sizeof(i64));
+        std::memcpy(anchor.mutable_data(), r.anchor.data(), (size_t)k * 2 * sizeof(i64));
+        std::memcpy(bbox.mutable_data(), r.bbox.data(), (size_t)k * 4 * sizeof(i64));
+        std::memcpy(pop.mutable_data(), r.population.data(), (size_t)k * sizeof(u32));
+    }
+    if (!r.hash.empty()) std::memcpy(hash.mutable_data(), r.hash.data(), r.hash.size() * sizeof(u64));
+    if (!r.per_board.empty()) std::memcpy(per.mutable_data(), r.per_board.data(), r.per_board.size() * sizeof(u32));
+    return py::make_tuple(r.count, board, anchor, pop, bbox, hash, r.truncated, per);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_gol, m) {
@@ -707,6 +725,33 @@ PYBIND11_MODULE(_gol, m) {
         .def("match_cells", [](Engine& e, const std::vector<std::pair<int, MatchTemplate>>& ts, uintptr_t ptr, int code, i64 numel) {
             cells_call([&](const CellBuffer& b) { e.match_cells(ts, b); }, ptr, code, numel);
         })
+        // connected components (gol/components.hpp): components_tuple(); what a call refuses is a ValueError, raised before
+        // anything is launched
+        .def(
+            "components",
+            [](Engine& e, const std::string& neighbourhood, i64 max_objects, bool hashes, bool records) {
+                ComponentsResult res;
+                try {
+                    const CcNeighbourhood nb = cc_neighbourhood(neighbourhood);
+                    py::gil_scoped_release r;
+                    res = e.components(nb, max_objects, hashes, records);
+                } catch (const Error& err) {
+                    throw py::value_error(err.what());
+                }
+                return components_tuple(res);
+            },
+            py::arg("neighbourhood") = "moore", py::arg("max_objects") = (i64)1 << 20, py::arg("hashes") = true,
+            py::arg("records") = true)
+        // (h, w) labels into the int32 or int64 buffer at ptr
+        .def("components_labels", [](Engine& e, const std::string& neighbourhood, uintptr_t ptr, bool int64, i64 numel) {
+            try {
+                const CcNeighbourhood nb = cc_neighbourhood(neighbourhood);
+                py::gil_scoped_release r;
+                e.components_labels(nb, reinterpret_cast<void*>(ptr), int64, numel);
+            } catch (const Error& err) {
+                throw py::value_error(err.what());
+            }
+        })
         .def("device_barrier", &Engine::device_barrier, py::call_guard<py::gil_scoped_release>())
         .def("phase_probe", &Engine::phase_probe, py::arg("k"), py::call_guard<py::gil_scoped_release>())
         .def("time_runs", &Engine::time_runs, py::arg("gens"), py::arg("reps"), py::call_guard<py::gil_scoped_release>())
@@ -809,6 +854,15 @@ PYBIND11_MODULE(_gol, m) {
     });
     m.def("write_rle", &write_rle);
     m.def("write_rle_file", &write_rle_file);
+
+    // measurement switch of tools/measure_components.py: components() on the HIP backends with (the default) or without
+    // the reduction across a wave in k_cc_stats and k_cc_hash; the results do not depend on it
+    m.def("cc_wave_reduce", [](bool on) { hipk::cc_set_wave_reduce(on); });
+    // the orientation-free hash (gol/components.hpp) of a 2-D 0/1 array as it stands
+    m.def("object_hash", [](py::array_t<u8, py::array::c_style | py::array::forcecast> cells) {
+        if (cells.ndim() != 2) throw py::value_error("object_hash: expected a 2-D array");
+        return object_hash_host(cells.data(), cells.shape(0), cells.shape(1));
+    });
 
     // ---- match templates (gol/match.hpp) ------------------------------------------------------
     // (what a builder or validate() refuses is a ValueError)
@@ -979,6 +1033,22 @@ PYBIND11_MODULE(_gol, m) {
                  if (!counts.empty()) std::memcpy(a.mutable_data(), counts.data(), counts.size() * sizeof(u32));
                  return a;
              })
+        // connected components of every soup: components_tuple(), `board` the soup's index
+        .def(
+            "components",
+            [](SoupBatch& b, const std::string& neighbourhood, i64 max_objects, bool hashes, bool records) {
+                ComponentsResult res;
+                try {
+                    const CcNeighbourhood nb = cc_neighbourhood(neighbourhood);
+                    py::gil_scoped_release r;
+                    res = b.components(nb, max_objects, hashes, records);
+                } catch (const Error& e) {
+                    throw py::value_error(e.what());
+                }
+                return components_tuple(res);
+            },
+            py::arg("neighbourhood") = "moore", py::arg("max_objects") = (i64)1 << 20, py::arg("hashes") = true,
+            py::arg("records") = true)
         .def("synchronize",
              [](SoupBatch& b) {
                  py::gil_scoped_release r;

@@ -181,6 +181,11 @@ std::vector<u32> SoupBatch::match_counts(const std::vector<std::vector<MatchTemp
     return out;
 }
 
+ComponentsResult SoupBatch::components(CcNeighbourhood nb, i64 max_objects, bool hashes, bool want_records) {
+    cc_check(cfg_.size, cfg_.size, cfg_.n, max_objects, "soups: components()");
+    return do_components(nb, max_objects, hashes, want_records);
+}
+
 SoupStats SoupBatch::stats() const {
     SoupStats s;
     s.kernel = strprintf("soups@%lld", (long long)cfg_.size) + (cfg_.rule.is_conway() ? "" : ":rule");
@@ -390,6 +395,11 @@ class CpuSoups final : public SoupBatch {
                 counts[i] = (u32)c;
             }
         }
+    }
+    ComponentsResult do_components(CcNeighbourhood nb, i64 max_objects, bool hashes, bool want_records) override {
+        std::vector<u64> nat((size_t)(cfg_.n * wps_));
+        for (size_t k = 0; k < nat.size(); ++k) nat[k] = merge_word(board_[k]);
+        return components_host(nat.data(), cfg_.size, cfg_.size, cfg_.n, true, nb, max_objects, hashes, want_records, nullptr);
     }
 
    private:

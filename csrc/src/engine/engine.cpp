@@ -1110,6 +1110,33 @@ void Engine::match_cells(const std::vector<std::pair<int, MatchTemplate>>& ts, c
 }
 
 // ---------------------------------------------------------------------------------------------
+// Connected components (gol/components.hpp; the backends label)
+// ---------------------------------------------------------------------------------------------
+
+void Engine::check_components(i64 max_objects, const char* what) const {
+    if (t_->size() > 1)
+        throw Error(strprintf("%s: this job has %d ranks; components are built for one rank (an object may cross a tile's "
+                              "edge)", what, t_->size()));
+    cc_check(g_.dec.H, g_.dec.W, 1, max_objects, what);
+}
+
+ComponentsResult Engine::components(CcNeighbourhood nb, i64 max_objects, bool hashes, bool want_records) {
+    check_components(max_objects, "components()");
+    return components_local(nb, max_objects, hashes, want_records);
+}
+
+void Engine::components_labels(CcNeighbourhood nb, void* dst, bool int64, i64 numel) {
+    check_components(1, "components_labels()");
+    if (numel != L_.h * L_.w)
+        throw Error(strprintf("components_labels(): the buffer holds %lld elements, the board %lld x %lld cells", (long long)numel,
+                              (long long)L_.h, (long long)L_.w));
+    const i64 size = int64 ? 8 : 4;
+    if (!dst || reinterpret_cast<uintptr_t>(dst) % (uintptr_t)size) throw Error("components_labels(): the buffer is not aligned to its element");
+    check_cell_pointer(CellBuffer{dst, CellType::U8, numel * size}, "components_labels()");
+    components_labels_cells(nb, dst, int64);
+}
+
+// ---------------------------------------------------------------------------------------------
 // CPU backend
 // ---------------------------------------------------------------------------------------------
 
@@ -1244,6 +1271,22 @@ class CpuEngine : public Engine {
         s.c0 = 0, s.W = L_.w;
         s.w0 = 0, s.gwords = L_.nw, s.fw = L_.nw;
         unpack_cells_host(s, dst);
+    }
+    // connected components: the host labeller on the board's natural-order words
+    ComponentsResult components_local(CcNeighbourhood nb, i64 max_objects, bool hashes, bool want_records) override {
+        std::vector<u64> d((size_t)(L_.h * L_.nw));
+        cpu::extract_words(cur_, L_, d.data());
+        return components_host(d.data(), L_.h, L_.w, 1, !dead_edges(), nb, max_objects, hashes, want_records, nullptr);
+    }
+    void components_labels_cells(CcNeighbourhood nb, void* dst, bool int64) override {
+        std::vector<u64> d((size_t)(L_.h * L_.nw));
+        cpu::extract_words(cur_, L_, d.data());
+        std::vector<i32> lab((size_t)(L_.h * L_.w));
+        components_host(d.data(), L_.h, L_.w, 1, !dead_edges(), nb, 1, false, false, lab.data());
+        if (int64)
+            std::copy(lab.begin(), lab.end(), static_cast<i64*>(dst));
+        else
+            std::copy(lab.begin(), lab.end(), static_cast<i32*>(dst));
     }
     size_t film_chunk() const override {  // (the host record between two drains stays below 64 MiB)
         return std::max<size_t>(8, ((size_t)64 << 20) / ((size_t)film_geo_.slot_words() * sizeof(u64)));

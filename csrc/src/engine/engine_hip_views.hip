@@ -117,6 +117,24 @@ void HipEngine::match_bitmap_cells(const CellBuffer& dst) {
     HIP_CHECK(hipStreamSynchronize(s_comp_));
 }
 
+// The objects of the canonical board.  Scratch (the parent array, four bytes per cell against the board's one bit, and
+// the records) is allocated for the call and freed before it returns (hipk::run_components, run_component_labels):
+// kept, the parent array would hold 32 times the board's bytes for the engine's lifetime for the sake of an occasional
+// call.  Keeping it was not measured.
+ComponentsResult HipEngine::components_local(CcNeighbourhood nb, i64 max_objects, bool hashes, bool want_records) {
+    sync_canonical();
+    synchronize();
+    check_res_status();
+    return hipk::run_components(buf_[cur_], hipk::match_geo(L_, !dead_edges()), nb, max_objects, hashes, want_records, s_comp_);
+}
+
+void HipEngine::components_labels_cells(CcNeighbourhood nb, void* dst, bool int64) {
+    sync_canonical();
+    synchronize();
+    check_res_status();
+    hipk::run_component_labels(buf_[cur_], hipk::match_geo(L_, !dead_edges()), nb, dst, int64, s_comp_);
+}
+
 void HipEngine::stamp_local(const RlePattern& p, i64 r0, i64 c0, StampMode mode) {
     check_stamp(p, r0, c0);
     sync_canonical();

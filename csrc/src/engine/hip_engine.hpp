@@ -121,6 +121,9 @@ class HipEngine : public Engine {
     u64 match_local(const MatchTemplate& t, bool keep, bool or_into) override;
     void match_positions_local(i64 cap, std::vector<i32>* out) override;
     void match_bitmap_cells(const CellBuffer& dst) override;
+    // connected components (engine_hip_views.hip; kernels: src/hip/components_kernel.hip)
+    ComponentsResult components_local(CcNeighbourhood nb, i64 max_objects, bool hashes, bool want_records) override;
+    void components_labels_cells(CcNeighbourhood nb, void* dst, bool int64) override;
 
     // dense cells on the device (engine_hip_cells.hip; kernels: src/hip/tensor_kernels.hip)
     void check_cell_pointer(const CellBuffer& b, const char* what) override;

@@ -121,6 +121,16 @@ class HipSoups final : public SoupBatch {
         HIP_CHECK(hipMemcpyAsync(counts, match_counts_, (size_t)cfg_.n * sizeof(u32), hipMemcpyDeviceToHost, stream_));
         HIP_CHECK(hipStreamSynchronize(stream_));
     }
+    // the kernels of src/hip/components_kernel.hip over the store, as k_match sees it
+    ComponentsResult do_components(CcNeighbourhood nb, i64 max_objects, bool hashes, bool want_records) override {
+        use();
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        hipk::MatchGeo g;
+        g.base = 0, g.pitch = m(), g.batch_stride = wps_;
+        g.w = cfg_.size, g.h = (i32)cfg_.size, g.nw = m();
+        g.torus = 1, g.batch = (i32)cfg_.n;
+        return hipk::run_components(board_, g, nb, max_objects, hashes, want_records, stream_);
+    }
 
    private:
     size_t bytes() const { return (size_t)cfg_.n * (size_t)wps_ * sizeof(u64); }

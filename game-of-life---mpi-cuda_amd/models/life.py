@@ -873,6 +873,62 @@ class Simulation:
         self.engine.match_cells(ts, *tensors.handle(t))
         return t
 
+    # -- connected components (ops/components.py states the neighbourhoods, the box rule and the hash) ----------
+    def components(self, neighbourhood: str = "moore", max_objects: int = 1 << 20, hashes: bool = True):
+        """The objects of the current board (under a Generations rule: of its live cells): :class:`ops.Components`
+        ``(count, anchor, population, bbox, hash, truncated)``, sorted by anchor.  ``neighbourhood``: ``"von_neumann"``,
+        ``"moore"`` or ``"moore2"`` (Chebyshev distance <= 2, the pseudo-object notion).  ``count`` is always exact; with
+        ``count > max_objects``, ``truncated`` is True and the arrays hold some ``max_objects`` of the objects, each
+        complete.  ``window(*bbox[i])`` is object ``i``; ``hash`` is the same for all eight orientations of an object, so
+        ``np.unique(objs.hash, return_counts=True)`` is a census.  ``hashes=False`` leaves ``hash`` empty.  One rank only.
+        On the HIP backend the board stays on the device: only the counter and the records leave it."""
+        from ..ops.components import Components
+
+        self._one_rank("components")  # (the native side refuses the neighbourhood, max_objects and 2^31 cells)
+        count, _, anchor, pop, bbox, h, truncated, _ = self.engine.components(neighbourhood, int(max_objects), bool(hashes), True)
+        return Components(int(count), anchor, pop, bbox, h, bool(truncated))
+
+    def count_components(self, neighbourhood: str = "moore") -> int:
+        """``components(...).count`` with nothing but the counter leaving the device."""
+        self._one_rank("count_components")
+        return int(self.engine.components(neighbourhood, 1, False, False)[0])
+
+    def components_tensor(self, neighbourhood: str = "moore", dtype=None, out=None):
+        """The labels as an ``(h, w)`` tensor on the simulation's side: ``1 + row * W + col`` of the anchor of the cell's
+        object, 0 for a dead cell.  ``dtype``: ``torch.int32`` (the default) or ``torch.int64``; ``out``, stream ordering
+        and errors as :meth:`match_tensor`."""
+        import torch
+
+        from ..ops import tensors
+        from ..ops.components import check_neighbourhood
+
+        what = "components_tensor"
+        self._two_states("components_tensor()")
+        check_neighbourhood(neighbourhood, what)  # (before a tensor is made; the native side checks the rest)
+        self._one_rank(what)
+        shape, device = (self.geometry.h, self.geometry.w), self._tensor_device()
+        if out is None:
+            dtype = torch.int32 if dtype is None else dtype
+            if dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"{what}: dtype {dtype} is not one of torch.int32, int64")
+            t = torch.empty(shape, dtype=dtype, device=device)
+        else:
+            if not isinstance(out, torch.Tensor):
+                raise ValueError(f"{what}: out must be a torch.Tensor, got {type(out).__name__}")
+            if tuple(out.shape) != shape:
+                raise ValueError(f"{what}: out has shape {tuple(out.shape)}, the result is {shape}")
+            if out.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"{what}: dtype {out.dtype} is not one of torch.int32, int64")
+            if dtype is not None and out.dtype != dtype:
+                raise ValueError(f"{what}: out has dtype {out.dtype}, the call asks for {dtype}")
+            if not out.is_contiguous():
+                raise ValueError(f"{what}: out is not contiguous (strides {tuple(out.stride())} for shape {tuple(out.shape)})")
+            tensors.check_device(out, device, what)
+            t = out
+        tensors.sync(t)
+        self.engine.components_labels(neighbourhood, t.data_ptr(), t.dtype == torch.int64, t.numel())
+        return t
+
     def load_rle(self, path, at="center") -> "Simulation":
         """An empty board (generation 0) with the file's pattern on it.  Raises if the file names a rule
         other than the simulation's."""

@@ -151,6 +151,22 @@ class SoupBatch:
                     raise ValueError(f"soups: match_counts: the template is {o.th} x {o.tw} cells, a soup {self.size} x {self.size}")
         return self._native.match_counts(templates)
 
+    def components(self, neighbourhood: str = "moore", max_objects: int = 1 << 20, hashes: bool = True):
+        """The objects of every soup's current board, each soup its own torus: :class:`ops.SoupComponents` ``(count, soup,
+        anchor, population, bbox, hash, truncated)`` sorted by ``(soup, row, col)``, anchors and boxes in the soup's own
+        coordinates; the arguments are :meth:`Simulation.components`'s.  HIP: the labelling kernels run once over the whole
+        store; only the counters and the records leave the device.  A pending :meth:`step` is included."""
+        from ..ops.components import SoupComponents
+
+        # (the native side refuses an unknown neighbourhood, max_objects < 1 and 2^31 cells or more, naming the value)
+        count, soup, anchor, pop, bbox, h, truncated, _ = self._native.components(neighbourhood, int(max_objects), bool(hashes), True)
+        return SoupComponents(int(count), soup, anchor, pop, bbox, h, bool(truncated))
+
+    def component_counts(self, neighbourhood: str = "moore") -> np.ndarray:
+        """An ``(n,)`` uint32 array: the objects of every soup.  Only the counters leave the device; a pending :meth:`step`
+        is included."""
+        return self._native.components(neighbourhood, 1, False, False)[7]
+
     def stats(self) -> dict:
         """``kernel`` (``soups@64``, ``soups@128``, ``soups@256``; ``:rule`` appended for the generic variant), ``launches``,
         ``settled``, ``reached`` (the generation of the unsettled soups), ``backend``, ``rule``, ``workgroup``."""

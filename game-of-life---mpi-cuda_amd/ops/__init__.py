@@ -32,6 +32,7 @@ from .cycle import Cycle, find_repeat  # noqa: F401
 from .tensors import evolve  # noqa: F401
 from .rle import parse_rle, pattern_cells, pattern_from_cells, write_rle  # noqa: F401
 from .match import MatchResult, Template, match_template, numpy_match, template_orientations  # noqa: F401
+from .components import Components, SoupComponents, numpy_components, object_hash  # noqa: F401
 from .._native import _gol as _native
 
 
